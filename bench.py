@@ -1,6 +1,12 @@
 """Training-throughput benchmark of the MI355X path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: set-up, W warm-up steps, K timed steps,
+the outputs of the last timed step to DIR (--dump-outputs) and the result line. --full adds,
+outside the timed region, everything else this benchmark measures: the roofline object (one
+extra profiled step after the timed ones), the training-summary mIoU, the EVAL path, the
+train.py leg and the CPU baseline (each still switched off by its own --no-* option).
 
 N > 1: `python bench.py --gpus N` launches N fresh rank processes itself (one per GPU, RCCL),
 as the reference's --distribute takes every visible GPU in one launch (system_factory.py:
@@ -19,9 +25,10 @@ moving-average update + the EMA of the model variables (N=1: the reference's sin
 default, ema_decay 0.9; distributed runs drop it, as the reference does). Weak scaling: 4
 images per GPU at every N.
 
-Prints ONE JSON line (rank 0) with the metric, a roofline object for the dominant kernel
-class (HIP-event timed inside the timed region) and the CPU baseline (the oracle — a
-PyTorch-CPU fp32 restatement of the reference semantics — timed on this host's cores).
+Prints ONE JSON line (rank 0) with the metric and `ms_per_step`; with --full also a roofline
+object for the dominant kernel class (HIP-event timed in one extra step after the timed
+region) and the CPU baseline (the oracle — a PyTorch-CPU fp32 restatement of the reference
+semantics — timed on this host's cores). The fields of the --full legs are null in a plain run.
 """
 import argparse
 import json
@@ -212,6 +219,36 @@ def train_py_leg(args, steps=10, warmup=3):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+DUMP_BUDGET_BYTES = 48 << 20   # all .npy files of one --dump-outputs together (limit: 64 MB)
+
+
+def dump_outputs(ctx, out_dir):
+    """--dump-outputs: what a caller of the timed step holds after its last step, as float32
+    `out_dir/<name>.npy`: the losses, the regularisation value and the low-resolution logits
+    (real class columns) of seg_outputs, and the state the update wrote (params, momentum, BN
+    moving statistics, EMA). An array larger than its share of DUMP_BUDGET_BYTES is written as
+    a fixed sample: the elements at sorted indices drawn once from a generator seeded by the
+    array's length, so two builds sample the same elements."""
+    import numpy as np
+    import torch
+    from seg_hip import DATASET
+    losses, reg, logits = ctx.outputs()
+    nc = sum((53, 12, 5) if ctx.cfg.dataset == DATASET["vistas"] else (14, 7, 3))
+    arrays = {"losses": losses, "reg": reg, "logits": logits[..., :nc], "params": ctx.params,
+              "momentum": ctx.momentum, "moving": ctx.moving}
+    if ctx.ema is not None:
+        arrays["ema"] = ctx.ema
+    cap = DUMP_BUDGET_BYTES // 4 // len(arrays)   # float32 elements per array
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(t.numel()).integers(0, t.numel(), cap))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float32))
+
+
 def launch_ranks(n, argv):
     """`bench.py --gpus N` without WORLD_SIZE: start N child processes of this script (never an
     exec of this one; utils/launch.spawn_ranks: rank r on GPU r, rendezvous on 127.0.0.1, the
@@ -258,6 +295,11 @@ def main():
                     help="default: the config's (ASPP as C2-C5 name it; none for C1)")
     ap.add_argument("--config", default="C2", choices=sorted(CONFIGS),
                     help="BASELINE.json workload preset (per-GPU share); C2 is the metric's")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs outside the headline figure: roofline profile, "
+                         "training-summary mIoU, EVAL path, train.py leg, CPU baseline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--no-eval", action="store_true")
@@ -268,6 +310,13 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    # the legs beside the headline figure run under --full only
+    do_profile = args.full and not args.no_profile
+    do_eval = args.full and not args.no_eval
+    do_train_py = args.full and not args.no_train_py
+    do_cpu = args.full and not args.no_cpu_baseline
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -365,14 +414,10 @@ def main():
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
-    # HIP-event kernel timing (roofline) is recorded on the launch stream during the LAST timed
-    # step only: events around every conv launch of every step cost ~1.8 ms per step
     if world > 1:
         timing[0] = comm_ev
     t0 = time.perf_counter()
-    for i in range(args.steps):
-        if i == args.steps - 1 and not args.no_profile:
-            ctx.profile(True)
+    for _ in range(args.steps):
         step()
     torch.cuda.synchronize()
     if world > 1:
@@ -402,9 +447,17 @@ def main():
     lv = losses.cpu().numpy()
     if not np.all(np.isfinite(lv)):
         raise RuntimeError(f"non-finite losses {lv}")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ctx, args.dump_outputs)
 
     roofline = None
-    if not args.no_profile:
+    if do_profile:
+        # HIP-event kernel timing (roofline) is recorded on the launch stream during ONE extra
+        # step after the timed region: events around every conv launch cost ~1.8 ms per step
+        # and the profiled step runs its backward on one stream
+        ctx.profile(True)
+        step()
+        torch.cuda.synchronize()
         cls = {c: ctx.profile_read(c) for c in (0, 1, 2)}
         # every profiled class against its own roofline: conv classes in TFLOP/s vs the bf16
         # MFMA peak, BN streaming classes in TB/s of algorithmic bytes vs HBM peak
@@ -525,7 +578,7 @@ def main():
     # the timed region and after the profiled step has been read; random-init weights, so it
     # only exercises the path (the reference's 70.46 needs trained weights and Cityscapes)
     miou = None
-    if nb_pp:
+    if args.full and nb_pp:
         from estimator.define_metrics import confusion_matrix, mean_iou_from_cm
         dec = torch.empty((nb_pp + nb_pb + nb_pi, H, W), dtype=torch.int32, device=dev)
         ctx.forward(img)
@@ -536,7 +589,7 @@ def main():
     # the timed training region: moving-statistics BN forward + seg_predict (fused decisions,
     # cid map, nearest resize at label size = network size) + device confusion matrix
     ev = None
-    if not args.no_eval and nb_pp:
+    if do_eval and nb_pp:
         from estimator.define_metrics import confusion_matrix
         from utils.utils import metrics_from_confusion_matrix
         cmap = list(range(19)) + [-1]
@@ -562,7 +615,7 @@ def main():
               "what": "moving-statistics BN forward + seg_predict + confusion (3 batches)"}
     ctx.close()
     train_py = None
-    if world == 1 and not args.no_train_py and args.config == "C2":
+    if world == 1 and do_train_py and args.config == "C2":
         # a failure of this side leg (host PNG encode, TFRecord writes, decode threads, a second
         # context) must not cost the headline line
         try:
@@ -574,7 +627,7 @@ def main():
             traceback.print_exc()
             train_py = {"error": repr(e)[:500]}
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "C2":
+    if rank == 0 and world == 1 and do_cpu and args.config == "C2":
         cpu = cpu_baseline(pyramid=args.pyramid)
 
     if world > 1 and comm["world_size"] != args.gpus:
@@ -583,7 +636,7 @@ def main():
         value = world * NB * args.steps / elapsed
         out = {"metric": "training images/sec at 1024x2048 bf16, 1/2/4/8 MI355X + mIoU vs ref",
                "value": round(value, 3), "unit": "images/sec", "n_gpus": world,
-               "steps": args.steps, "warmup": args.warmup,
+               "steps": args.steps, "warmup": args.warmup, "full": args.full,
                "ms_per_step": round(elapsed * 1e3 / args.steps, 2),
                "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
                "dtype": args.dtype, "data": "synthetic (seeded; random-init weights)",

@@ -267,6 +267,13 @@ def test_bench_world_size_must_match_gpus():
     assert '{"metric"' not in r.stdout
 
 
+def test_bench_rejects_zero_timed_steps():
+    """--steps is the number of timed steps: a run without one has no ms_per_step to report."""
+    r = _run_bench(["--gpus", "1", "--steps", "0", "--warmup", "1"], {})
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr, r.stderr
+    assert '{"metric"' not in r.stdout
+
+
 def test_bench_launches_ranks_and_propagates_failure():
     """`bench.py --gpus 2` with no WORLD_SIZE starts two rank processes of itself (RANK /
     LOCAL_RANK / WORLD_SIZE / MASTER_* set, 127.0.0.1). Here (no GPU) both ranks fail at device

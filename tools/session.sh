@@ -30,8 +30,8 @@ for step in "$@"; do
     suite) timeout -k 10 900 python3 -u -m pytest tests -x -q -m gpu --timeout 300 --timeout-method thread > "$out/suite.txt" 2>&1 ;;
     tests) timeout -k 10 900 python3 -u -m pytest -x -v --timeout ${TT:-600} --timeout-method thread ${val//,/ } >> "$out/tests.txt" 2>&1 ;;
     smoke) timeout -k 10 300 python3 -u -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.txt" 2>&1 ;;
-    bench) timeout -k 10 500 python3 -u bench.py --gpus 1 --steps 20 --warmup 5 > "$out/bench.json" 2> "$out/bench.err" ;;
-    benchq) timeout -k 10 300 python3 -u bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-eval --no-train-py > "$out/benchq.json" 2> "$out/benchq.err" ;;
+    bench) timeout -k 10 500 python3 -u bench.py --gpus 1 --steps 20 --warmup 5 --full > "$out/bench.json" 2> "$out/bench.err" ;;
+    benchq) timeout -k 10 300 python3 -u bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-eval --no-train-py > "$out/benchq.json" 2> "$out/benchq.err" ;;
     multi) SEG_BENCH_BACKEND=gloo timeout -k 10 600 python3 -u bench.py --gpus "$val" --steps 2 --warmup 1 --no-eval --no-train-py --no-cpu-baseline > "$out/multi$val.json" 2> "$out/multi$val.err" ;;
     stats)
       SEG_SIDE_STREAM=0 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$out/stats" -o run -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-eval --no-train-py > "$out/stats.log" 2>&1
