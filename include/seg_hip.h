@@ -289,6 +289,16 @@ int seg_op_conv_wgrad_cfg(int dtype, const void* dy, int N, int Ho, int Wo, int 
                           const void* x, int H, int W, int Ci, int ldx, int k, int stride, int rate,
                           int explicit_pad, float* dw, void* workspace, int64_t ws_bytes, int bm,
                           int bn, int splits, void* stream);
+/* the fused data-gradient launches of the runtime, stride 1, k in {1, 3} (rate 1 for k = 1),
+ * SAME geometry: dx = dgrad(dy) [+ dy2 . wt2 (1 x 1, Co2 channels)] [+ r1] [+ r2], stored masked
+ * by omask (as seg_op_conv_dgrad_res; NULL = unmasked). wt [Ci][k][k][Co] flipped, wt2 [Ci][Co2];
+ * r1 may alias dx. -EINVAL for the combinations the runtime never launches: r2 without r1, dy2
+ * with a residual, with k = 3 or with a 32-bit dtype, a mask where no masked launch exists */
+int seg_op_conv_dgrad_fused(int dtype, const void* dy, int N, int H, int W, int Co, int lddy,
+                            const void* wt, int Ci, int k, int rate, void* dx, int lddx,
+                            const void* r1, int ldr1, const void* r2, int ldr2, const void* dy2,
+                            int Co2, int lddy2, const void* wt2, const uint8_t* omask,
+                            void* stream);
 
 #ifdef __cplusplus
 }

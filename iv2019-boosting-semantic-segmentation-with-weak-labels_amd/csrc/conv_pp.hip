@@ -669,12 +669,23 @@ __device__ __forceinline__ void conv_nt_pp_body(const ConvArgs& a) {
 #pragma unroll
       for (int qn = 0; qn < 2; ++qn) {
         char* const hw = hres[qn] + wn * 16384;
-        // this wave's residual of half qn landed (each wave adds only what it fetched); half 1:
-        // half 0's 8 stores, the next tile's 16 mask loads and 8 K-tile-0 pieces are younger
+        // this wave's residual of half qn landed (each wave adds only what it fetched). The
+        // counts, from the wave's issue order (the main loop's last wait, vmcnt(8), left only
+        // half 0's 8 pieces outstanding; vector memory operations retire in issue order):
+        //   half 0: its 8 pieces, then half 1's 8 pieces                        -> vmcnt(8)
+        //   half 1, ragged tile: a wave whose lanes all fail the store's bounds test may
+        //     branch around it, so half 0's stores cannot be counted            -> vmcnt(0)
+        //   half 1, full tile, a next tile: half 0's 8 stores, then (after the barrier) the
+        //     next tile's 16 mask loads -- issued only with a mask -- and its 8 K-tile-0
+        //     pieces are younger: 8 + 16 + 8 with a mask                        -> vmcnt(32)
+        //     8 + 8 without one (vmcnt(32) there would wait for nothing)        -> vmcnt(16)
+        //   half 1, full tile, the last tile: half 0's 8 stores are younger     -> vmcnt(8)
         if (qn == 0) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
         else if (!fullt) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (has_next) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+        else if (has_next) {
+          if (omask) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");   // wave-uniform
+          else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+        } else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
         PP_TS(dbg_it, 4 + 3 * qn);
         // in place, accumulator layout: dx = round(dgrad + r), one rounding
         u32x2_t rr[2][4][2];

@@ -781,6 +781,29 @@ int gn_backward(Step& S, int li, const Act& dz0, int dz_f32, const Act* z0, cons
   return 0;
 }
 
+// a data gradient as a forward problem over dy [N][Ho][Wo][Co] with the flipped, transposed
+// weights wt [Ci][k][k][Co], into dx [N][H][W][Ci]; (pad_h, pad_w) = the forward conv's padding.
+// Shared by the network's launches (dgrad_args) and the op entry seg_op_conv_dgrad_fused
+ConvArgs dgrad_conv_args(const void* dy, int N, int Ho, int Wo, int Co, int lddy, const void* wt,
+                         int Ci, int k, int stride, int rate, int pad_h, int pad_w, int H, int W,
+                         void* dx, int lddx) {
+  ConvArgs a{};
+  a.x = dy; a.N = N; a.H = Ho; a.W = Wo; a.C = Co; a.ldx = lddy;
+  a.w = wt; a.ldw = k * k * Co;
+  a.y = dx; a.Ho = H; a.Wo = W; a.Co = Ci; a.ldy = lddx;
+  a.KH = a.KW = k;
+  const int keff = k + (k - 1) * (rate - 1);
+  a.sf = 1; a.st = stride;
+  a.pad_h = (keff - 1) - pad_h; a.pad_w = (keff - 1) - pad_w;
+  a.dil = rate; a.stats = nullptr;
+  return a;
+}
+// the K-concatenated second data gradient (1 x 1, the same pixels): dx += dy2 . wt2
+void dgrad_dual_args(ConvArgs& a, const void* dy2, int lddy2, int Co2, const void* wt2) {
+  a.x2 = dy2; a.ldx2 = lddy2; a.C2 = Co2;
+  a.w2 = wt2; a.ldw2 = Co2;
+}
+
 // dx = dgrad(dy) [+ r1] [+ r2]
 ConvArgs dgrad_args(seg_ctx* c, int li, const Act& dx, const Act* r1, const Act* r2);
 
@@ -817,8 +840,7 @@ int conv_dgrad_dual(Step& S, int li, int li2, const Act& dx, const uint8_t** oma
       !L.wt_lp || !L2.wt_lp)
     return 1;
   ConvArgs a = dgrad_args(c, li, dx, nullptr, nullptr);
-  a.x2 = L2.dy.p; a.ldx2 = L2.dy.ld; a.C2 = L2.co;
-  a.w2 = L2.wt_lp; a.ldw2 = L2.co;
+  dgrad_dual_args(a, L2.dy.p, L2.dy.ld, L2.co, L2.wt_lp);
   if (a.st != 1 || a.sf != 1 || a.pad_h || a.pad_w || !conv_nt_pp_ok(a)) return 1;
   if (omask && *omask) {   // stored masked by the consumer's ReLU bits where that launch exists
     a.omask = *omask; a.ldm = a.Co / 8;
@@ -836,17 +858,10 @@ int conv_dgrad_dual(Step& S, int li, int li2, const Act& dx, const uint8_t** oma
 
 ConvArgs dgrad_args(seg_ctx* c, int li, const Act& dx, const Act* r1, const Act* r2) {
   ConvL& L = c->convs[li];
-  ConvArgs a{};
-  a.x = L.dy.p; a.N = L.N; a.H = L.Ho; a.W = L.Wo; a.C = L.co; a.ldx = L.dy.ld;
-  a.w = L.wt_lp; a.ldw = L.k * L.k * L.co;
-  a.y = dx.p; a.Ho = L.H; a.Wo = L.W; a.Co = L.ci; a.ldy = dx.ld;
+  ConvArgs a = dgrad_conv_args(L.dy.p, L.N, L.Ho, L.Wo, L.co, L.dy.ld, L.wt_lp, L.ci, L.k, L.stride,
+                               L.rate, L.pad_h, L.pad_w, L.H, L.W, dx.p, dx.ld);
   if (r1) { a.r = r1->p; a.ldr = r1->ld; }
   if (r2) { a.r2 = r2->p; a.ldr2 = r2->ld; }
-  a.KH = a.KW = L.k;
-  const int keff = L.k + (L.k - 1) * (L.rate - 1);
-  a.sf = 1; a.st = L.stride;
-  a.pad_h = (keff - 1) - L.pad_h; a.pad_w = (keff - 1) - L.pad_w;
-  a.dil = L.rate; a.stats = nullptr;
   return a;
 }
 
@@ -2543,6 +2558,44 @@ int seg_op_conv_dgrad_res(int dtype, const void* dy, int N, int H, int W, int Co
   if (omask) { a.omask = omask; a.ldm = Ci / 8; }
   hipError_t e = launch_conv_nt(dt_of(dtype), 0, a, (hipStream_t)stream);
   return e == hipSuccess ? 0 : hip_fail(nullptr, e, "seg_op_conv_dgrad_res");
+}
+
+int seg_op_conv_dgrad_fused(int dtype, const void* dy, int N, int H, int W, int Co, int lddy,
+                            const void* wt, int Ci, int k, int rate, void* dx, int lddx,
+                            const void* r1, int ldr1, const void* r2, int ldr2, const void* dy2,
+                            int Co2, int lddy2, const void* wt2, const uint8_t* omask, void* stream) {
+  if (!dy || !wt || !dx || N < 1 || H < 1 || W < 1 || Co < 1 || Ci < 1)
+    return set_err(nullptr, -EINVAL, "dgrad_fused: bad argument");
+  if ((k != 1 && k != 3) || rate < 1 || (k == 1 && rate != 1))
+    return set_err(nullptr, -EINVAL, "dgrad_fused: k must be 1 (rate 1) or 3");
+  if (r2 && !r1) return set_err(nullptr, -EINVAL, "dgrad_fused: a second residual needs a first");
+  if ((dy2 != nullptr) != (wt2 != nullptr))
+    return set_err(nullptr, -EINVAL, "dgrad_fused: dy2 and wt2 come together");
+  // the combinations the runtime launches: a dual GEMM has no residual (conv_dgrad_dual)
+  if (dy2 && (r1 || r2 || k != 1 || !seg_half(dt_of(dtype)) || Co2 < 1))
+    return set_err(nullptr, -EINVAL, "dgrad_fused: the dual GEMM is 1 x 1, 16-bit, without residuals");
+  int ho, wo, ph, pw;
+  op_geom(H, W, k, 1, rate, 0, &ho, &wo, &ph, &pw);   // stride 1, SAME: ho = H, wo = W
+  ConvArgs a = dgrad_conv_args(dy, N, H, W, Co, lddy, wt, Ci, k, 1, rate, ph, pw, H, W, dx, lddx);
+  if (r1) { a.r = r1; a.ldr = ldr1; }
+  if (r2) { a.r2 = r2; a.ldr2 = ldr2; }
+  if (dy2) dgrad_dual_args(a, dy2, lddy2, Co2, wt2);
+  if (omask) {
+    if (Ci % 8) return set_err(nullptr, -EINVAL, "dgrad_fused: masked outputs need Ci %% 8 == 0");
+    a.omask = omask; a.ldm = Ci / 8;
+    if (!conv_nt_omask_ok(dt_of(dtype), a))
+      return set_err(nullptr, -EINVAL, "dgrad_fused: no masked launch for this shape");
+  }
+  hipError_t e;
+  if (dy2 && Ci > 128) {   // as conv_dgrad_dual: the ping-pong kernel's K-concatenated GEMM
+    if (!conv_nt_pp_ok(a)) return set_err(nullptr, -EINVAL, "dgrad_fused: dual shape not on the ping-pong path");
+    e = launch_conv_nt_pp(dt_of(dtype), a, (hipStream_t)stream);
+  } else {
+    if (dy2 && !(conv_nt_v2_ok(a) && conv_nt_v2_dual_ok(a)))
+      return set_err(nullptr, -EINVAL, "dgrad_fused: dual shape not on the v2 path");
+    e = launch_conv_nt(dt_of(dtype), 0, a, (hipStream_t)stream);
+  }
+  return e == hipSuccess ? 0 : hip_fail(nullptr, e, "seg_op_conv_dgrad_fused");
 }
 
 int seg_op_conv_wgrad(int dtype, const void* dy, int N, int Ho, int Wo, int Co, int lddy,
