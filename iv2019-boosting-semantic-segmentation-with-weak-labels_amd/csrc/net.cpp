@@ -2407,7 +2407,13 @@ int seg_debug_tensor(seg_ctx* c, const char* name, void** ptr, int* dims, int* l
                                       st.pad_h, st.pad_w, 0));
       HIPCALL(c, hipDeviceSynchronize());
       a.p = c->img_dbg; a.N = st.N; a.H = st.H; a.W = st.W; a.C = 3; a.ld = 8;
-    } else if (n.substr(us) == "_x") a = c->convs[i].x;
+    } else if (n.substr(us) == "_x") {
+      a = c->convs[i].x;
+      if (!a.p) {   // before the first forward (which binds the input): the layer's geometry alone
+        const ConvL& L = c->convs[i];
+        a.N = L.N; a.H = L.H; a.W = L.W; a.C = L.ci;
+      }
+    }
     else if (n.substr(us) == "_y") a = c->convs[i].y;
     else if (n.substr(us) == "_dy") {
       ConvL& L = c->convs[i];

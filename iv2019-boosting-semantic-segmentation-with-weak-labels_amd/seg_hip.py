@@ -432,6 +432,13 @@ class SegContext:
             t = _wrap_u16(ptr.value, (n * hh * ww, ld.value), self.device, half=dt.value == 2)
         return t[:, :c].float().cpu().numpy().reshape(n, hh, ww, c)
 
+    def debug_dims(self, name: str):
+        """(N, H, W, C) of an internal tensor; a conv's input has them from seg_create on, its
+        pointer only after the first forward (geometry tests read the dims without a step)."""
+        dims = (ctypes.c_int * 4)()
+        check(LIB.seg_debug_tensor(self.h, name.encode(), None, dims, None, None), self.h)
+        return tuple(dims)
+
     def debug_device(self, name: str):
         """Zero-copy device view [N,H,W,C] (storage dtype, pixel stride ld) of an internal
         tensor: the full-size parity tests read 1024 x 2048 activations without a host copy."""

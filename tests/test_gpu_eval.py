@@ -60,7 +60,9 @@ def _ctx(cfg, dtype="fp32"):
 
 
 CFGS = [SegConfig(height=64, width=128, nb_pp=2, pyramid="psp"),
-        SegConfig(height=48, width=64, nb_pp=1, pyramid="aspp")]
+        SegConfig(height=48, width=64, nb_pp=1, pyramid="aspp"),
+        # 621 x 855's parity class: mixed max-pool pads, PSP windows on a 13 x 13 map
+        SegConfig(height=101, width=103, nb_pp=2, pyramid="psp")]
 
 
 @pytest.mark.parametrize("cfg", CFGS, ids=lambda c: f"{c.height}x{c.width}-{c.pyramid}")

@@ -18,7 +18,10 @@ stem and the transposed-stride dgrad.
   the ASPP transposes, the stem max-pool), against a float64 restatement fed the tensors the
   native step itself consumed (``oracle/conv_props.py``, pinned to ``conv_tf`` and autograd by
   ``tests/test_oracle.py``); plus the loss terms and fused decisions of the loss head against
-  ``OracleNet.losses`` / ``head_predictions`` on the native low-resolution logits.
+  ``OracleNet.losses`` / ``head_predictions`` on the native low-resolution logits. The checker
+  is ``tests/step_chain.py`` (shared with ``tests/test_gpu_odd_geometry.py``); its forward
+  links (BN + ReLU, max-pool, unit outputs with their shortcuts, pyramid glue, each native
+  16-bit tensor against the float64 restatement of the op that wrote it) are on here too.
 
 Tolerances (written per check below):
 * 16-bit outputs (forward y, data gradients of the op tests): per element
@@ -33,51 +36,13 @@ Tolerances (written per check below):
 """
 import math
 
-import numpy as np
 import pytest
 import torch
 
-from oracle.conv_props import conv_dgrad, conv_fwd, conv_wgrad
-from oracle.tfseg import BN_EPS, ConvSpec, OracleNet, SegConfig, build_specs, conv_tf, init_params, resnet_units
+from oracle.tfseg import ConvSpec, SegConfig, conv_tf
+from step_chain import ABI, TDT, ULP, _elementwise, step_chain
 
 pytestmark = pytest.mark.gpu
-
-TDT = {"bf16": torch.bfloat16, "fp16": torch.float16}
-ABI = {"bf16": 1, "fp16": 2}
-ULP = {"bf16": 2.0 ** -8, "fp16": 2.0 ** -11}
-
-
-def _elementwise(got, ref, rtol, atol_rms, what, absref=None, n_sum=0):
-    """|got - ref| <= rtol |ref| + atol_rms rms(ref) [+ 2^-24 sqrt(n_sum) absref]: absref =
-    the same sum over |terms| (an fp32 sum of n_sum terms in any order is off by ~sqrt(n) ulps
-    of the absolute sum, which matters where the signed sum cancels)."""
-    got = got.double()
-    ref = ref.double().to(got.device)
-    rms = float(ref.pow(2).mean().sqrt())
-    bound = rtol * ref.abs() + atol_rms * rms
-    if absref is not None:
-        bound = bound + 2.0 ** -24 * math.sqrt(n_sum) * absref
-    excess = (got - ref).abs() / bound
-    nbad = int((excess > 1).sum())
-    assert nbad == 0, f"{what}: {nbad} of {ref.numel()} elements out of tolerance " \
-                      f"(worst {float(excess.max()):.3g}x the bound)"
-
-
-def _tiles(got, ref, tol, tile_tol, what, rows=256):
-    """L2-relative over the tensor and over every `rows`-pixel tile of the NHWC pixel order."""
-    C = ref.shape[-1]
-    g = got.double().reshape(-1, C)
-    r = ref.double().reshape(-1, C).to(g.device)
-    rel = float((g - r).norm() / r.norm().clamp_min(1e-300))
-    assert rel < tol, f"{what}: rel {rel:.3g}"
-    M = r.shape[0]
-    pad = (-M) % rows
-    e2 = torch.nn.functional.pad((g - r).pow(2).sum(1), (0, pad)).reshape(-1, rows).sum(1)
-    r2 = torch.nn.functional.pad(r.pow(2).sum(1), (0, pad)).reshape(-1, rows).sum(1)
-    floor = 1e-2 * float(r2.mean())   # tiles the ReLU mask zeroed almost entirely
-    trel = (e2 / r2.clamp_min(floor)).sqrt()
-    worst = int(trel.argmax())
-    assert float(trel[worst]) < tile_tol, f"{what}: tile {worst} of {len(trel)} rel {float(trel[worst]):.3g}"
 
 
 # ------------------------------------------------------------------------- single layers
@@ -173,43 +138,7 @@ def test_conv_c2_layer(cuda, case, dtype):
 
 
 # ------------------------------------------------------------------------- one full C2 step
-def _bn_bwd(dz, y, z, gamma, y_exact):
-    """TF fused-BN training backward of [relu](bn(y)) (z = the ReLU output whose positives
-    pass the gradient, None = no ReLU), float64: dy = g * invstd * (dh - mean dh - xh mean(dh xh)).
-    The batch moments come from y_exact (the unrounded conv output: the native statistics are
-    reduced from the fp32 accumulators in the conv epilogue), x-hat from the stored y the
-    native BN backward reads. With 4 nearly equal samples (the ASPP image-pool branch: means of
-    random images) moments of the 16-bit y would be off by more than the batch spread."""
-    C = y.shape[-1]
-    ye = y_exact.double().reshape(-1, C)
-    dh = dz.double() if z is None else dz.double() * (z > 0)
-    dh = dh.reshape(-1, C)
-    mu = ye.mean(0)
-    inv = torch.rsqrt(ye.var(0, unbiased=False) + BN_EPS)
-    xh = (y.double().reshape(-1, C) - mu) * inv
-    out = gamma * inv * (dh - dh.mean(0) - xh * (dh * xh).mean(0))
-    return out.reshape(y.shape)
-
-
-def _maxpool_bwd(z0, g):
-    """3x3 / 2 SAME max-pool backward: the gradient goes to the first maximum of each window
-    in row-major scan order (TF MaxPoolGrad), padding never selected."""
-    N, H, W, C = z0.shape
-    Ho, Wo = g.shape[1], g.shape[2]
-    ph = max((Ho - 1) * 2 + 3 - H, 0) // 2
-    pw = max((Wo - 1) * 2 + 3 - W, 0) // 2
-    zp = torch.full((N, H + 2, W + 2, C), -math.inf, dtype=torch.float64, device=z0.device)
-    zp[:, ph:ph + H, pw:pw + W] = z0
-    taps = [zp[:, i:i + 2 * (Ho - 1) + 1:2, j:j + 2 * (Wo - 1) + 1:2] for i in range(3) for j in range(3)]
-    am = torch.stack(taps, 0).argmax(0)     # first maximum
-    del taps
-    acc = torch.zeros_like(zp)
-    for t in range(9):
-        i, j = divmod(t, 3)
-        acc[:, i:i + 2 * (Ho - 1) + 1:2, j:j + 2 * (Wo - 1) + 1:2] += g * (am == t)
-    return acc[:, ph:ph + H, pw:pw + W]
-
-
+# the chain checker itself is tests/step_chain.py (shared with tests/test_gpu_odd_geometry.py)
 # BASELINE configs at their per-GPU shape (1024 x 2048, 4 images): C2 as the bench runs it;
 # C4 = R101 + pyramid with the 1:2:1 strong : bbox : tag mix in bf16 (covers C3's kernels and
 # adds the weak-label loss head); C5 = the same mix in fp16 with fp32 master gradients under a
@@ -223,208 +152,17 @@ FULL_CONFIGS = [
     ("C4", 101, "bf16", (1, 2, 1), "aspp"),
     ("C5", 101, "fp16", (1, 2, 1), "aspp"),
 ]
+FULL_LINKS = True   # the forward links of step_chain, at full size too
 
 
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize("name,depth,dtype,mix,pyramid", FULL_CONFIGS, ids=[c[0] for c in FULL_CONFIGS])
 def test_step_layerwise_fullsize(cuda, name, depth, dtype, mix, pyramid):
-    from input_pipelines.synthetic import batch
-    from seg_hip import SegContext
-    H, W = 1024, 2048
     npp, npb, npi = mix
-    NB = npp + npb + npi
-    cfg = SegConfig(depth=depth, height=H, width=W, nb_pp=npp, nb_pb=npb, nb_pi=npi, pyramid=pyramid)
-    params = {k: v.astype(np.float32) for k, v in init_params(cfg, seed=2).items()}
-    data = batch(17, npp, npb, npi, H, W)
-    ctx = SegContext(depth=depth, pyramid=pyramid, height=H, width=W, nb_pp=npp, nb_pb=npb,
-                     nb_pi=npi, dtype=dtype)
-    ctx.load_params(params)
-    if dtype == "fp16":
-        ctx.set_loss_scale(4096.0)
-    dec = torch.zeros((NB, H, W), dtype=torch.int32, device=cuda)
-    ctx.forward(torch.as_tensor(data["images"]).to(cuda))
-    dev = lambda a: None if a is None else torch.as_tensor(a).to(cuda)
-    ctx.loss(dev(data["px"]), dev(data["bbox"]), dev(data["tag"]), dec)
-    losses, _, logits = ctx.outputs()
-    ctx.backward()
-    torch.cuda.synchronize()
-    assert bool(torch.isfinite(ctx.grads).all()), "non-finite gradients"
-    u = ULP[dtype]
-    specs = build_specs(cfg)
-    idx = {s.name: i for i, s in enumerate(specs)}
-    info = {p.name: p for p in ctx.param_info}
-
-    def X(i):
-        return ctx.debug_device(f"conv{i}_x").double()
-
-    def Y(i):
-        return ctx.debug_device(f"conv{i}_y").double()
-
-    def DY(i):
-        return ctx.debug_device(f"conv{i}_dy").double()
-
-    def Wt(i):   # the weights the step ran with (16-bit copies of the fp32 masters)
-        return torch.as_tensor(params[specs[i].name + "/weights"]).to(cuda).to(TDT[dtype]).double()
-
-    def gamma(i):
-        return torch.as_tensor(params[specs[i].name + "/BatchNorm/gamma"], dtype=torch.float64, device=cuda)
-
-    def native_grad(i):
-        p = info[specs[i].name + "/weights"]
-        return ctx.grads[p.offset:p.offset + p.numel].view(p.shape)
-
-    # conv3 layers the linear BN-backward fold took (csrc/lbf.h): their weight gradient was
-    # formed from the affine dz3 = A dyhat + B + D z3 without rounding dz3 to 16 bits (so the
-    # 16-bit dz3 the apply would have stored is no reference for it: its rounding errors follow
-    # z3 wherever the gate is closed and do not average out, 2.4-2.8e-3 of the gradient on
-    # these layers, profiles/r05_lbf_diag.txt); the reference is that affine form in float64
-    # from the step's coefficients and gated gradient with the exact conv output. The
-    # coefficients themselves are checked through dz3 (chk below: the apply on the same inputs
-    # against the float64 BN backward)
-    folded = set()
-    if ctx.counter("lbf_layers") > 0:
-        for i, s in enumerate(specs):
-            try:
-                ctx.debug_device(f"conv{i}_lbfcoef")
-                folded.add(i)
-            except Exception:
-                pass
-
-    # ---- every conv: forward output and weight gradient (the stem's 3 real channels of tap8)
-    for i, s in enumerate(specs):
-        x = X(i)
-        _elementwise(Y(i), conv_fwd(x, Wt(i), s), 2 * u, 1e-3, f"fwd {s.name}")
-        if i in folded:
-            coef = ctx.debug_device(f"conv{i}_lbfcoef").double().reshape(3, -1)
-            dy = coef[0] * ctx.debug_device(f"conv{i}_dyhat").double() + coef[1] + \
-                coef[2] * conv_fwd(x, Wt(i), s)
-        else:
-            dy = DY(i)
-        _elementwise(native_grad(i), conv_wgrad(x, dy, s), 1e-3, 1e-4, f"wgrad {s.name}",
-                     absref=conv_wgrad(x.abs(), dy.abs(), s), n_sum=dy[..., 0].numel())
-        del dy
-        del x
-
-    def chk(i, dz, z, what):
-        ye = conv_fwd(X(i), Wt(i), specs[i])
-        _tiles(DY(i), _bn_bwd(dz, Y(i), z, gamma(i), ye), 2e-2, 5e-2, f"{what} -> dy {specs[i].name}")
-
-    def dgrad(i, like):
-        return conv_dgrad(DY(i), Wt(i), specs[i], like.shape[1], like.shape[2])
-
-    def unit_chain(scope, g_out, out):
-        """conv3 (+ projection shortcut) from the unit-output gradient, then conv3 -> conv2 ->
-        conv1 inside the unit; returns the gradient w.r.t. the unit input."""
-        i1, i2, i3 = idx[f"{scope}/conv1"], idx[f"{scope}/conv2"], idx[f"{scope}/conv3"]
-        chk(i3, g_out, out, f"{scope} out")
-        isc = idx.get(f"{scope}/shortcut")
-        if isc is not None:
-            chk(isc, g_out, out, f"{scope} out")
-        chk(i2, dgrad(i3, X(i3)), X(i3), f"{scope} conv3 dgrad")
-        chk(i1, dgrad(i2, X(i2)), X(i2), f"{scope} conv2 dgrad")
-        xin = X(i1)
-        g_in = dgrad(i1, xin)
-        m = g_out * (out > 0)
-        if isc is not None:
-            g_in += dgrad(isc, xin)
-        elif m.shape[1] == xin.shape[1]:
-            g_in += m
-        else:   # resnet_utils.subsample: identity shortcut read at stride 2
-            g_in[:, ::2, ::2] += m
-        return g_in
-
-    # ---- heads: logits dgrad -> head unit; dfeat = sum over heads (identity shortcuts)
-    dfeat = None
-    for h in ("l1", "l2_vehicle", "l2_human"):
-        il = idx[f"softmax_classifier/{h}_logits"]
-        out = X(il)
-        g = unit_chain(f"adaptation_module/{h}_features", dgrad(il, out), out)
-        dfeat = g if dfeat is None else dfeat + g
-    pm = "feature_extractor/pyramid_module"
-    fd = cfg.feature_dims_decreased
-    idfd = idx["feature_extractor/extension/decrease_fdims"]
-    if pyramid == "aspp":
-        # ---- ASPP: final 1x1 over the 1280-channel concat, four conv branches, image pool
-        ifin = idx[f"{pm}/Conv_5"]
-        concat = X(ifin)
-        chk(ifin, dfeat, X(idx["adaptation_module/l1_features/conv1"]), "dfeat")
-        dconcat = dgrad(ifin, concat)
-        dz_dfd = 0
-        for b in range(1, 5):
-            ib = idx[f"{pm}/Conv_{b}"]
-            chk(ib, dconcat[..., b * fd:(b + 1) * fd], concat[..., b * fd:(b + 1) * fd], "ASPP concat")
-            dz_dfd = dz_dfd + dgrad(ib, X(ib))
-        ip = idx[f"{pm}/Conv"]
-        chk(ip, dconcat[..., :fd].sum((1, 2), keepdim=True), concat[:, :1, :1, :fd], "ASPP image pool")
-        dz_dfd = dz_dfd + dgrad(ip, X(ip)) / (X(ifin).shape[1] * X(ifin).shape[2])
-        chk(idfd, dz_dfd, X(idx[f"{pm}/Conv_1"]), "ASPP inputs")
-    else:
-        # ---- PSP (hierarchical.py:186-207): concat = [z | resize(relu(bn(conv(avgpool_k(z)))))
-        # for the grids k = 1, 2, 3, 6], the 1280 -> 256 Conv_4 over it. Forward: the pooled
-        # inputs (VALID windows of (hf/8, wf/8) // k, remainder rows / columns dropped) and the
-        # align-corners resizes into the concat; backward: the resize transposes, the branch BN
-        # backward gated by the branch's own ReLU output, the branch data gradients and the
-        # average-pool transposes summed with the identity slice into decrease_fdims' output
-        # gradient. float64 references; pooling and resizing by torch on the device
-        import torch.nn.functional as F
-        from oracle.tfseg import psp_grids
-        ifin = idx[f"{pm}/Conv_4"]
-        concat = X(ifin)
-        z = concat[..., :fd].permute(0, 3, 1, 2)                       # NCHW, decrease_fdims output
-        hf, wf = z.shape[2], z.shape[3]
-        chk(ifin, dfeat, X(idx["adaptation_module/l1_features/conv1"]), "dfeat")
-        dconcat = dgrad(ifin, concat)
-        dz_dfd = dconcat[..., :fd].clone()
-        grids = psp_grids(H, W)
+    cfg = SegConfig(depth=depth, height=1024, width=2048, nb_pp=npp, nb_pb=npb, nb_pi=npi, pyramid=pyramid)
+    rep = step_chain(cuda, cfg, dtype, param_seed=2, data_seed=17,
+                     loss_scale=4096.0 if dtype == "fp16" else None, links=FULL_LINKS,
+                     bn_tol=2e-2, tile_tol=5e-2)
+    if pyramid == "psp":
+        grids = rep["psp_grids"]
         assert grids[2] == (42, 85) and grids[3] == (21, 42)          # the dropped remainders
-        for b, nm in enumerate(["Conv", "Conv_1", "Conv_2", "Conv_3"]):
-            ib = idx[f"{pm}/{nm}"]
-            kh, kw = grids[b]
-            pooled = F.avg_pool2d(z, (kh, kw), stride=(kh, kw)).permute(0, 2, 3, 1)
-            _elementwise(X(ib), pooled, 2 * u, 1e-3, f"PSP pool {nm} ({kh}x{kw})")
-            zb = ctx.debug_device(f"pyr{b}_z").double()
-            up = F.interpolate(zb.permute(0, 3, 1, 2), size=(hf, wf), mode="bilinear",
-                               align_corners=True).permute(0, 2, 3, 1)
-            _elementwise(concat[..., (b + 1) * fd:(b + 2) * fd], up, 2 * u, 1e-3, f"PSP resize {nm}")
-            src = torch.zeros_like(zb.permute(0, 3, 1, 2), requires_grad=True)
-            F.interpolate(src, size=(hf, wf), mode="bilinear", align_corners=True).backward(
-                dconcat[..., (b + 1) * fd:(b + 2) * fd].permute(0, 3, 1, 2))
-            dzb = src.grad.permute(0, 2, 3, 1)
-            chk(ib, dzb, zb, f"PSP resize transpose {nm}")
-            dpool = dgrad(ib, X(ib))
-            zin = torch.zeros_like(z, requires_grad=True)
-            F.avg_pool2d(zin, (kh, kw), stride=(kh, kw)).backward(dpool.permute(0, 3, 1, 2))
-            dz_dfd += zin.grad.permute(0, 2, 3, 1)
-            del zb, up, src, dzb, dpool, zin
-        chk(idfd, dz_dfd, concat[..., :fd], "PSP inputs")
-    # ---- encoder units, top down, through residual / subsample / projection shortcuts
-    rn = f"feature_extractor/base/resnet_v1_{depth}"
-    scopes = [f"{rn}/{unit[0]}" for unit in resnet_units(depth, 8)]
-    g_out, out = dgrad(idfd, X(idfd)), X(idfd)
-    for k in reversed(range(len(scopes))):
-        g_out = unit_chain(scopes[k], g_out, out)
-        out = X(idx[f"{scopes[k]}/conv1"])
-    # ---- stem: max-pool backward -> ReLU mask -> BN backward
-    z0 = ctx.debug_device("z0").double()
-    chk(0, _maxpool_bwd(z0, g_out), z0, "max-pool")
-    del z0, g_out, out, dfeat, dconcat, concat, dz_dfd
-
-    # ---- loss head on the native low-resolution logits (define_losses_hierarchical.py:98-210)
-    net = OracleNet(cfg, params)
-    lg = logits.double().cpu()
-    low = {}
-    c0 = 0
-    for key, c in (("l1_logits", 14), ("l2_vehicle_logits", 7), ("l2_human_logits", 3)):
-        low[key] = lg[..., c0:c0 + c].permute(0, 3, 1, 2).contiguous()
-        c0 += c
-    L = net.losses(low, data["px"], data["bbox"], data["tag"])
-    ref = [float(L[k]) for k in ("segmentation", "l1_segmentation", "l2_vehicle_segmentation",
-                                  "l2_human_segmentation")]
-    lv = losses.cpu().numpy()
-    np.testing.assert_allclose(lv[:4], ref, rtol=1e-4)
-    for a, b in zip(lv[4:7], L["counts"]):   # weak weights follow the l1 argmax (near-ties)
-        assert abs(int(a) - int(b)) <= (0 if npb + npi == 0 else max(2, 1e-5 * int(b)))
-    _, _, _, fused = net.head_predictions(low)
-    mism = float((dec.cpu().long() != fused).double().mean())
-    assert mism < 1e-5, f"fused decisions differ on {mism:.2e} of the pixels"
-    ctx.close()

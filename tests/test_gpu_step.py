@@ -86,6 +86,10 @@ CONFIGS = [
     # norm_layer='group' (hierarchical.py:293-333): group_norm(32) everywhere, groups=1 on the
     # logits, PSP branches normalised over their pooled grids
     SegConfig(height=64, width=128, nb_pp=1, nb_pb=1, pyramid="psp", norm="group"),
+    # odd sizes (tests/test_gpu_odd_geometry.py): 621 x 855's parity class with the max-pool
+    # pads (1, 0) and the PSP windows on a 13 x 13 map; all-odd maps through block1's stride
+    SegConfig(height=101, width=103, nb_pp=1, nb_pb=1, pyramid="psp"),
+    SegConfig(height=97, width=145, nb_pp=1, nb_pb=1, nb_pi=1, pyramid="aspp"),
 ]
 
 
@@ -678,8 +682,13 @@ LOSS_GRAD = [SegConfig(height=48, width=64, nb_pp=1, nb_pb=1, pyramid="none"),
              SegConfig(height=64, width=96, nb_pp=1, nb_pb=1, nb_pi=1, pyramid="psp"),
              SegConfig(height=64, width=128, nb_pp=2, pyramid="aspp"),
              SegConfig(height=64, width=512, nb_pp=1, nb_pb=1, pyramid="none"),
-             SegConfig(height=48, width=1024, nb_pp=1, nb_pb=1, nb_pi=1, pyramid="none")]
-YF_SHAPES = {(64, 512), (48, 1024)}
+             SegConfig(height=48, width=1024, nb_pp=1, nb_pb=1, nb_pi=1, pyramid="none"),
+             # odd align-corners tables 13 -> 101 / 103 and 13 -> 97, 19 -> 145. loss_head_yf
+             # (csrc/loss.hip): 31 cells of (W - 1) / (Wl - 1) columns + 3 <= 256 threads, i.e.
+             # 31 * 102 / 12 + 3 = 266.5 (per-row kernel) and 31 * 144 / 18 + 3 = 251 (y-first)
+             SegConfig(height=101, width=103, nb_pp=1, nb_pb=1, pyramid="none"),
+             SegConfig(height=97, width=145, nb_pp=1, nb_pb=1, nb_pi=1, pyramid="none")]
+YF_SHAPES = {(64, 512), (48, 1024), (97, 145)}
 
 
 @pytest.mark.parametrize("cfg", LOSS_GRAD, ids=lambda c: f"{c.height}x{c.width}-{c.nb_pp}{c.nb_pb}{c.nb_pi}-{c.pyramid}")
