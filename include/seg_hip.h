@@ -244,6 +244,70 @@ int seg_bbox_labels(const float* boxes, const int32_t* cids, const int32_t* box_
                     void* stream);
 int seg_tag_labels(const float* tags, int n, int H, int W, float* out, void* stream);
 
+/* seg_bbox_labels with a per-image mirror (random_flipping applied to a bbox-weak image and its
+ * label map, augmentation_library.py:298-321): flip is device int32 [n], a nonzero entry makes
+ * output pixel x rasterise column W-1-x of the unflipped map; NULL = no image flipped. */
+int seg_bbox_labels_flip(const float* boxes, const int32_t* cids, const int32_t* box_off,
+                         const int32_t* geom, const int32_t* flip, int n, int max_boxes, int H,
+                         int W, float* out, void* stream);
+
+/* training augmentation on the device (preprocessing/augmentation_library.py: random_color
+ * :359-406, random_flipping :298-321, random_scaling :21-296; random_blur is not built), the call
+ * block the reference's train pipelines hold between the resize and from_0_1_to_m1_1
+ * (input_cityscapes.py:106-118). The random draws are the caller's: one record per image, and
+ * the kernels are pure functions of (raw input, record). Per image: resize (as
+ * seg_prepare_images_crop) -> colour -> flip stage -> scaling -> (x - 0.5) / 0.5.
+ *   colour  color_order -1 = none, else the op order 0: B S H C, 1: S B C H, 2: C H B S,
+ *           3: H S C B, then clip to [0, 1]. B: x + brightness_delta; S / H: through HSV,
+ *           s = clip(s * saturation_factor, 0, 1) / h = frac(h + hue_delta);
+ *           C: (x - m) * contrast_factor + m, m = per-channel mean of the image entering the op
+ *   flip    quantize = 1 (the stage is enabled): the image goes through uint8 (trunc(x * 255.5))
+ *           and back (q * (1 / 255)), flipped or not; flip = 1 mirrors image and label in x
+ *   scale   scale_mode 0 none; 1 up: crop (sh, sw) at (oy, ox), uint8 round trip, legacy bilinear
+ *           resize back to H x W (labels: nearest); 2 down: legacy bilinear resize to (sh, sw)
+ *           (labels: nearest) placed at ((H - sh) / 2, (W - sw) / 2), the rest filled with the
+ *           scalar mean of the resized image (labels: void_cid)
+ * A record is SEG_AUG_PARAMS_BYTES = 64 bytes. */
+#define SEG_AUG_PARAMS_BYTES 64
+typedef struct seg_aug_params {
+  int32_t color_order;
+  float brightness_delta, saturation_factor, hue_delta, contrast_factor;
+  int32_t quantize, flip;
+  int32_t scale_mode;
+  int32_t sh, sw;
+  int32_t oy, ox;
+  int32_t void_cid;
+  int32_t reserved[3];   /* pads the record to 64 bytes; ignored */
+} seg_aug_params;
+/* The table is passed twice: params_host (host memory) is validated before anything is launched
+ * and supplies the host-divided resize scales, params_dev (device memory, the same n records) is
+ * what the kernels read. -EINVAL with a seg_last_error text, and no launch, for: a scaled size
+ * outside 1..H x 1..W, a crop outside the image, color_order outside -1..3, scale_mode outside
+ * 0..2, a window outside the resized image, a workspace smaller than seg_augment_workspace says,
+ * out or workspace not 16-byte aligned.
+ * seg_augment_images: raw uint8 [n][src_h][src_w][3] + the geometry of seg_prepare_images_crop
+ *   (plain resize: resized = H x W, crop 0, 0) -> fp32 [n][H][W][3]. workspace (device) holds the
+ *   stage between the colour pass and the geometric pass and the partial sums of the two means;
+ *   both means are reduced in a fixed order (no atomics): same inputs, bitwise same output.
+ *   With an all-off record the output is bitwise seg_prepare_images_crop's.
+ * seg_augment_labels: raw uint8 ids [n][src_h][src_w] + lids2cids as seg_prepare_labels -> one
+ *   gather (scaling's nearest resize / void_cid pad, flip, the prepare step's nearest resize)
+ *   -> int32 [n][H][W]. Colour fields are ignored. */
+int seg_augment_workspace(int n, int H, int W, int64_t* bytes);
+int seg_augment_images(const uint8_t* raw, int n, int src_h, int src_w, int resized_h,
+                       int resized_w, int crop_y, int crop_x, int H, int W,
+                       const seg_aug_params* params_host, const seg_aug_params* params_dev,
+                       float* out, void* workspace, int64_t ws_bytes, void* stream);
+int seg_augment_labels(const uint8_t* raw, int n, int src_h, int src_w, int H, int W,
+                       const int32_t* lids2cids, int n_lids, const seg_aug_params* params_host,
+                       const seg_aug_params* params_dev, int32_t* out, void* stream);
+/* pass timing of seg_augment_images (diagnostics, tools/aug_table.py; no reference counterpart):
+ * enable != 0 makes later calls record events around their four passes (contrast mean, colour,
+ * down-scale mean, geometry); with pass_ms != NULL the call first waits for the last recorded
+ * call and stores its four pass times in milliseconds (0 for a skipped pass). Synchronises; not
+ * for use while a stream is being captured. */
+int seg_augment_profile(int enable, float* pass_ms);
+
 /* internal tensors for parity tests: "logits", "grad_un", "dzscale", "feat", "dfeat", "z0",
  * "head<h>_out", "head<h>_dout", "pyr<b>_z" (pyramid branch b's BN + ReLU output at its pooled
  * resolution), "conv<i>_x" (input of the last forward), "conv<i>_y", "conv<i>_dy" (i =

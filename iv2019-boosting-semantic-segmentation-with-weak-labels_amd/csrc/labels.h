@@ -22,8 +22,10 @@ struct BboxGeom {   // per image
 };
 
 // boxes [total][4] = (xmin, xmax, ymin, ymax) normalised, cids [total], box_off [n+1] prefix
-// offsets per image, geom [n]; out [n][H][W][15] fp32
+// offsets per image, geom [n]; flip [n] (NULL = none): a nonzero entry mirrors that image's map
+// in x (output pixel x rasterises column W-1-x); out [n][H][W][15] fp32
 hipError_t launch_bbox_labels(const float* boxes, const int* cids, const int* box_off,
-                              const BboxGeom* geom, int n, int H, int W, float* out, hipStream_t s);
+                              const BboxGeom* geom, const int* flip, int n, int H, int W, float* out,
+                              hipStream_t s);
 // tags [n][15] (already normalised) -> out [n][H][W][15]
 hipError_t launch_tag_labels(const float* tags, int n, int H, int W, float* out, hipStream_t s);

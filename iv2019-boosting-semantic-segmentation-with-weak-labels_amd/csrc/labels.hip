@@ -13,7 +13,7 @@ constexpr int LB_MAX_BOXES = 1024;   // reference MAX_N_BBOXES = 516 (input_subs
 // 256 x 15 floats through LDS as contiguous 16-byte chunks.
 __global__ __launch_bounds__(LB_THREADS) void bbox_labels_kernel(const float* boxes, const int* cids,
                                                               const int* box_off, const BboxGeom* geom,
-                                                              int H, int W, float* out) {
+                                                              const int* flip, int H, int W, float* out) {
   __shared__ int4 rect[LB_MAX_BOXES];
   __shared__ int rcid[LB_MAX_BOXES];
   __shared__ float stage[LB_THREADS * SEG_WEAK_CLASSES];
@@ -34,7 +34,9 @@ __global__ __launch_bounds__(LB_THREADS) void bbox_labels_kernel(const float* bo
   const long p = (long)blockIdx.x * LB_THREADS + threadIdx.x;
   float v[SEG_WEAK_CLASSES];
   if (p < npix) {
-    const int y = (int)(p / W), x = (int)(p - (long)y * W);
+    const int y = (int)(p / W), xo = (int)(p - (long)y * W);
+    // a mirrored image (random_flipping on the resized + cropped map): pixel x shows column W-1-x
+    const int x = (flip && flip[img]) ? W - 1 - xo : xo;
     // TF 1.12 ResizeNearestNeighbor (align_corners = false): float scale in/out, floorf
     const float sh = (float)g.src_h / (float)g.rh, sw = (float)g.src_w / (float)g.rw;
     const int sy = min((int)floorf((float)(y + g.oy) * sh), g.src_h - 1);
@@ -86,11 +88,12 @@ __global__ __launch_bounds__(LB_THREADS) void tag_labels_kernel(const float* tag
 }  // namespace
 
 hipError_t launch_bbox_labels(const float* boxes, const int* cids, const int* box_off,
-                              const BboxGeom* geom, int n, int H, int W, float* out, hipStream_t s) {
+                              const BboxGeom* geom, const int* flip, int n, int H, int W, float* out,
+                              hipStream_t s) {
   if (n <= 0) return hipSuccess;
   const long npix = (long)H * W;
   const dim3 grid((unsigned)ceil_div(npix, LB_THREADS), (unsigned)n);
-  hipLaunchKernelGGL(bbox_labels_kernel, grid, dim3(LB_THREADS), 0, s, boxes, cids, box_off, geom, H, W, out);
+  hipLaunchKernelGGL(bbox_labels_kernel, grid, dim3(LB_THREADS), 0, s, boxes, cids, box_off, geom, flip, H, W, out);
   return hipGetLastError();
 }
 

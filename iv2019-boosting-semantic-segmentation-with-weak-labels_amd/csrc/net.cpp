@@ -16,6 +16,7 @@
 #include "bn.h"
 #include "lbf.h"
 #include "input.h"
+#include "augment.h"
 #include "conv.h"
 #include "deconv.h"
 #include "gn.h"
@@ -2299,17 +2300,31 @@ int seg_stream_wait_bucket(seg_ctx* c, int bucket, void* stream) {
   return 0;
 }
 
+static int bbox_labels(const char* who, const float* boxes, const int32_t* cids,
+                       const int32_t* box_off, const int32_t* geom, const int32_t* flip, int n,
+                       int max_boxes, int H, int W, float* out, void* stream) {
+  if (n < 0 || H <= 0 || W <= 0 || (n > 0 && (!box_off || !geom || !out)))
+    return set_err(nullptr, -EINVAL, "%s: bad arguments", who);
+  if (max_boxes < 0 || max_boxes > 1024)
+    return set_err(nullptr, -E2BIG, "%s: at most 1024 boxes per image (reference 516)", who);
+  static_assert(sizeof(BboxGeom) == 6 * sizeof(int32_t), "geom layout");
+  hipError_t e = launch_bbox_labels(boxes, cids, box_off, (const BboxGeom*)geom, flip, n, H, W, out,
+                                    (hipStream_t)stream);
+  return e == hipSuccess ? 0 : hip_fail(nullptr, e, who);
+}
+
 int seg_bbox_labels(const float* boxes, const int32_t* cids, const int32_t* box_off,
                     const int32_t* geom, int n, int max_boxes, int H, int W, float* out,
                     void* stream) {
-  if (n < 0 || H <= 0 || W <= 0 || (n > 0 && (!box_off || !geom || !out)))
-    return set_err(nullptr, -EINVAL, "seg_bbox_labels: bad arguments");
-  if (max_boxes < 0 || max_boxes > 1024)
-    return set_err(nullptr, -E2BIG, "seg_bbox_labels: at most 1024 boxes per image (reference 516)");
-  static_assert(sizeof(BboxGeom) == 6 * sizeof(int32_t), "geom layout");
-  hipError_t e = launch_bbox_labels(boxes, cids, box_off, (const BboxGeom*)geom, n, H, W, out,
-                                    (hipStream_t)stream);
-  return e == hipSuccess ? 0 : hip_fail(nullptr, e, "seg_bbox_labels");
+  return bbox_labels("seg_bbox_labels", boxes, cids, box_off, geom, nullptr, n, max_boxes, H, W, out,
+                     stream);
+}
+
+int seg_bbox_labels_flip(const float* boxes, const int32_t* cids, const int32_t* box_off,
+                         const int32_t* geom, const int32_t* flip, int n, int max_boxes, int H,
+                         int W, float* out, void* stream) {
+  return bbox_labels("seg_bbox_labels_flip", boxes, cids, box_off, geom, flip, n, max_boxes, H, W,
+                     out, stream);
 }
 
 int seg_tag_labels(const float* tags, int n, int H, int W, float* out, void* stream) {
@@ -2352,6 +2367,80 @@ int seg_prepare_labels(const uint8_t* raw, int n, int src_h, int src_w, int H, i
     m.cid[i] = lids2cids[i] == -1 ? mx + 1 : lids2cids[i];
   hipError_t e = launch_prepare_labels(raw, n, src_h, src_w, H, W, m, out, (hipStream_t)stream);
   return e == hipSuccess ? 0 : hip_fail(nullptr, e, "seg_prepare_labels");
+}
+
+static LidMap lid_map(const int32_t* lids2cids, int n_lids) {
+  LidMap m{};
+  m.n = n_lids;
+  int mx = -1;
+  for (int i = 0; i < n_lids; ++i) mx = std::max(mx, (int)lids2cids[i]);
+  for (int i = 0; i < n_lids; ++i)   // utils._replacevoids: -1 -> max + 1
+    m.cid[i] = lids2cids[i] == -1 ? mx + 1 : lids2cids[i];
+  return m;
+}
+
+static_assert(sizeof(seg_aug_params) == sizeof(AugParams) && sizeof(AugParams) == SEG_AUG_PARAMS_BYTES,
+              "seg_aug_params layout");
+
+// the shared checks of the two augmentation entries: the table is validated from the caller's
+// host copy before anything is launched
+static int aug_check(const char* who, int n, int H, int W, const seg_aug_params* params_host,
+                     const seg_aug_params* params_dev) {
+  if (n > 0 && (!params_host || !params_dev))
+    return set_err(nullptr, -EINVAL, "%s: the parameter table is required on the host and on the device", who);
+  char msg[256];
+  if (aug_validate((const AugParams*)params_host, n, H, W, msg, sizeof msg))
+    return set_err(nullptr, -EINVAL, "%s: %s", who, msg);
+  return 0;
+}
+
+int seg_augment_workspace(int n, int H, int W, int64_t* bytes) {
+  if (n < 0 || H <= 0 || W <= 0 || !bytes)
+    return set_err(nullptr, -EINVAL, "seg_augment_workspace: bad arguments");
+  *bytes = (int64_t)aug_workspace_bytes(n, H, W);
+  return 0;
+}
+
+int seg_augment_profile(int enable, float* pass_ms) {
+  hipError_t e = aug_profile_enable(enable != 0);
+  if (e == hipSuccess && pass_ms) e = aug_profile_read(pass_ms);
+  return e == hipSuccess ? 0 : hip_fail(nullptr, e, "seg_augment_profile");
+}
+
+int seg_augment_images(const uint8_t* raw, int n, int src_h, int src_w, int resized_h,
+                       int resized_w, int crop_y, int crop_x, int H, int W,
+                       const seg_aug_params* params_host, const seg_aug_params* params_dev,
+                       float* out, void* workspace, int64_t ws_bytes, void* stream) {
+  if (n < 0 || src_h <= 0 || src_w <= 0 || H <= 0 || W <= 0 || (n > 0 && (!raw || !out)))
+    return set_err(nullptr, -EINVAL, "seg_augment_images: bad arguments");
+  if (crop_y < 0 || crop_x < 0 || (int64_t)crop_y + H > resized_h || (int64_t)crop_x + W > resized_w)
+    return set_err(nullptr, -EINVAL, "seg_augment_images: window %d,%d + %dx%d outside the resized "
+                   "%dx%d", crop_y, crop_x, H, W, resized_h, resized_w);
+  if (int r = aug_check("seg_augment_images", n, H, W, params_host, params_dev)) return r;
+  if (((uintptr_t)out & 15) || ((uintptr_t)workspace & 15))
+    return set_err(nullptr, -EINVAL, "seg_augment_images: out / workspace must be 16-byte aligned");
+  const int64_t need = (int64_t)aug_workspace_bytes(n, H, W);
+  if (n > 0 && (!workspace || ws_bytes < need))
+    return set_err(nullptr, -EINVAL, "seg_augment_images: workspace of %lld bytes, %lld needed "
+                   "(seg_augment_workspace)", (long long)ws_bytes, (long long)need);
+  const AugResize r{src_h, src_w, resized_h, resized_w, crop_y, crop_x};
+  hipError_t e = launch_augment_images(raw, n, r, H, W, (const AugParams*)params_host,
+                                       (const AugParams*)params_dev, out, workspace,
+                                       (hipStream_t)stream);
+  return e == hipSuccess ? 0 : hip_fail(nullptr, e, "seg_augment_images");
+}
+
+int seg_augment_labels(const uint8_t* raw, int n, int src_h, int src_w, int H, int W,
+                       const int32_t* lids2cids, int n_lids, const seg_aug_params* params_host,
+                       const seg_aug_params* params_dev, int32_t* out, void* stream) {
+  if (n < 0 || src_h <= 0 || src_w <= 0 || H <= 0 || W <= 0 || (n > 0 && (!raw || !out)) ||
+      !lids2cids || n_lids <= 0 || n_lids > SEG_MAX_LIDS)
+    return set_err(nullptr, -EINVAL, "seg_augment_labels: bad arguments");
+  if (int r = aug_check("seg_augment_labels", n, H, W, params_host, params_dev)) return r;
+  hipError_t e = launch_augment_labels(raw, n, src_h, src_w, H, W, lid_map(lids2cids, n_lids),
+                                       (const AugParams*)params_host, (const AugParams*)params_dev,
+                                       out, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : hip_fail(nullptr, e, "seg_augment_labels");
 }
 
 int seg_debug_tensor(seg_ctx* c, const char* name, void** ptr, int* dims, int* ld, int* dtype) {

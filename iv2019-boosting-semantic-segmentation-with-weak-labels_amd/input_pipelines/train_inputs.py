@@ -36,6 +36,18 @@ selection runs in order on the calling thread, the PNG / JPEG decodes of the nex
 ``--input_prefetch`` batches run on a pool of ``--input_workers`` threads (PIL releases the
 GIL while it decodes), and each batch's uploads + device preprocessing are issued when the
 training loop takes it.
+
+Augmentation (``--augment_color``, ``--augment_flip``, ``--augment_scale LOW HIGH``; all off by
+default: input_pipelines/augment.py). With a flag on, every stream's images go through
+``seg_augment_images`` instead of ``seg_prepare_images[_crop]``: the per-pixel stream gets
+colour + flip + scaling (its labels through ``seg_augment_labels``), the bbox and tag streams
+colour + flip only (their dense labels are float multinomials, which random_scaling asserts
+against, augmentation_library.py:97, and they already random-crop an aspect-preserving
+resize). A flipped bbox image carries its flag as a 6th element of its ``BoxLists`` item and
+is rasterised mirrored (``seg_bbox_labels_flip``); tag sets are flip-invariant. The draws come
+from a third generator per stream, ``default_rng([seed, s, rank, 2])``, so the shuffles and
+crop offsets are what they are without augmentation; with the flags off no augmentation
+kernel is launched and the batches are unchanged.
 """
 from __future__ import annotations
 
@@ -177,14 +189,16 @@ def _weak_geometry(src, H, W, rng):
     return rs, off
 
 
-def box_item(boxes, src, H, W, rng):
+def box_item(boxes, src, H, W, rng, flip=None):
     """One BoxLists item from index boxes [[mid, [xmin, xmax, ymin, ymax]], ...]: unknown mids
-    are dropped (the reference's mid2cid lookup covers the subset's classes only)."""
+    are dropped (the reference's mid2cid lookup covers the subset's classes only). With `flip`
+    (0 / 1, an enabled flip stage) the item carries it as a 6th element."""
     kept = [(MID2CID[m], c) for m, c in boxes if m in MID2CID]
     cids = np.asarray([k for k, _ in kept], np.int32)
     coords = np.asarray([c for _, c in kept], np.float32).reshape(len(kept), 4)
     rs, off = _weak_geometry(src, H, W, rng)
-    return (cids, coords, tuple(src), rs, off)
+    item = (cids, coords, tuple(src), rs, off)
+    return item if flip is None else item + (int(flip),)
 
 
 def heterogeneous_train_input(config, params) -> Callable:
@@ -193,6 +207,7 @@ def heterogeneous_train_input(config, params) -> Callable:
     {'prolabels_per_pixel': int32 [Nb_pp, H, W], 'prolabels_per_bbox': BoxLists,
     'prolabels_per_image': TagSets}. Decoding runs ahead on a thread pool (module docstring)."""
     import torch
+    from input_pipelines.augment import augment_images, augment_labels, draw_params
     from input_pipelines.tfrecords import prepare_images, prepare_images_crop, prepare_labels
     from input_pipelines.utils import get_temp_Nb
     rank, world = _rank_world()
@@ -203,6 +218,14 @@ def heterogeneous_train_input(config, params) -> Callable:
     rngs = [np.random.default_rng([seed, s, rank]) for s in range(3)]
     geom = [np.random.default_rng([seed, s, rank, 1]) for s in range(3)]   # crop offsets
     lids2cids = list(params.training_problem_def['lids2cids'])
+    a_color = bool(getattr(params, 'augment_color', False))
+    a_flip = bool(getattr(params, 'augment_flip', False))
+    a_scale = getattr(params, 'augment_scale', None)
+    a_scale = None if a_scale is None or tuple(a_scale) == (1.0, 1.0) else tuple(a_scale)
+    aug_pp = a_color or a_flip or a_scale is not None      # per-pixel: colour + flip + scaling
+    aug_weak = a_color or a_flip                           # bbox / tag: colour + flip
+    aug = [np.random.default_rng([seed, s, rank, 2]) for s in range(3)]   # augmentation draws
+    void_cid = max(lids2cids) + 1
     pp = PerPixelStream(params.tfrecords_path_per_pixel, rngs[0], rank, world) if nb[0] else None
     if nb[1] and not (params.bboxes_index_path and params.bboxes_images_dir):
         raise ValueError('Nb_per_bbox > 0 needs --bboxes_index_path and --bboxes_images_dir')
@@ -241,11 +264,21 @@ def heterogeneous_train_input(config, params) -> Callable:
             if 'pp' in job:
                 ex = [f.result() for f in job['pp']]
                 same = len({e[0].shape for e in ex}) == 1
+                ap = draw_params(aug[0], len(ex), H, W, color=a_color, flip=a_flip,
+                                 scale_poi=a_scale, void_cid=void_cid) if aug_pp else None
                 if same:   # one upload + one launch for the sub-batch
                     raw_i = torch.from_numpy(np.stack([e[0] for e in ex])).pin_memory().to(dev, non_blocking=True)
                     raw_l = torch.from_numpy(np.stack([e[1] for e in ex])).pin_memory().to(dev, non_blocking=True)
-                    ims.append(prepare_images(raw_i, H, W))
-                    px = prepare_labels(raw_l, H, W, lids2cids)
+                    if aug_pp:
+                        ims.append(augment_images(raw_i, ap, H, W))
+                        px = augment_labels(raw_l, ap, H, W, lids2cids)
+                    else:
+                        ims.append(prepare_images(raw_i, H, W))
+                        px = prepare_labels(raw_l, H, W, lids2cids)
+                elif aug_pp:
+                    ims += [augment_images(to_dev(e[0]), ap[i:i + 1], H, W) for i, e in enumerate(ex)]
+                    px = torch.cat([augment_labels(to_dev(e[1]), ap[i:i + 1], H, W, lids2cids)
+                                    for i, e in enumerate(ex)])
                 else:
                     ims += [prepare_images(to_dev(e[0]), H, W) for e in ex]
                     px = torch.cat([prepare_labels(to_dev(e[1]), H, W, lids2cids) for e in ex])
@@ -254,17 +287,22 @@ def heterogeneous_train_input(config, params) -> Callable:
                 if kind not in job:
                     continue
                 g = geom[1] if kind == 'bbox' else geom[2]
-                for iid, ann, fut in job[kind]:
+                ap = draw_params(aug[1 if kind == 'bbox' else 2], len(job[kind]), H, W,
+                                 color=a_color, flip=a_flip, void_cid=void_cid) if aug_weak else None
+                for i, (iid, ann, fut) in enumerate(job[kind]):
                     im = fut.result()
                     src = im.shape[:2]
                     if kind == 'bbox':
-                        item = box_item(ann, src, H, W, g)
+                        item = box_item(ann, src, H, W, g, int(ap['flip'][i]) if a_flip else None)
                         boxes.append(item)
                         rs, off = item[3], item[4]
                     else:
                         tags.append([MID2CID[m] for m in ann if m in MID2CID])
                         rs, off = _weak_geometry(src, H, W, g)
-                    ims.append(prepare_images_crop(to_dev(im), rs, off, H, W))
+                    if aug_weak:
+                        ims.append(augment_images(to_dev(im), ap[i:i + 1], H, W, resized=rs, offset=off))
+                    else:
+                        ims.append(prepare_images_crop(to_dev(im), rs, off, H, W))
             feats = {'proimages': torch.cat(ims) if len(ims) > 1 else ims[0]}
             labels = {'prolabels_per_pixel': px,
                       'prolabels_per_bbox': boxes if nb[1] else None,

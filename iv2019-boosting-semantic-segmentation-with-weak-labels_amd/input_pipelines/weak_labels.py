@@ -83,10 +83,14 @@ class BboxLabelsGPU:
 
     def bbox(self, images, out=None, stream=None):
         """images: list of (cids, coords (k, 4) = (xmin, xmax, ymin, ymax), src_size (h, w),
-        resized_size (h, w), offset (y, x)). Returns a device tensor [n, H, W, 15]."""
+        resized_size (h, w), offset (y, x)[, flip]). Returns a device tensor [n, H, W, 15]; an
+        item with flip = 1 (random_flipping of that image, input_pipelines/augment.py) is
+        rasterised mirrored in x (seg_bbox_labels_flip, called only when a flag is set)."""
         import torch
         from seg_hip import LIB, check
         n = len(images)
+        flips = np.asarray([int(im[5]) if len(im) > 5 else 0 for im in images], np.int32)
+        images = [tuple(im[:5]) for im in images]
         counts = [len(im[0]) for im in images]
         if max(counts, default=0) > 1024:
             raise ValueError("at most 1024 boxes per image (reference MAX_N_BBOXES = 516)")
@@ -111,8 +115,14 @@ class BboxLabelsGPU:
         if out is None:
             out = torch.empty((n, self.h, self.w, N_WEAK_CLASSES), dtype=torch.float32, device=dev)
         s = (stream or torch.cuda.current_stream()).cuda_stream
-        check(LIB.seg_bbox_labels(tb.data_ptr(), tc.data_ptr(), to.data_ptr(), tg.data_ptr(), n,
-                                  max(counts, default=0), self.h, self.w, out.data_ptr(), s))
+        if flips.any():
+            tf = torch.as_tensor(flips).to(dev)
+            check(LIB.seg_bbox_labels_flip(tb.data_ptr(), tc.data_ptr(), to.data_ptr(),
+                                           tg.data_ptr(), tf.data_ptr(), n, max(counts, default=0),
+                                           self.h, self.w, out.data_ptr(), s))
+        else:
+            check(LIB.seg_bbox_labels(tb.data_ptr(), tc.data_ptr(), to.data_ptr(), tg.data_ptr(), n,
+                                      max(counts, default=0), self.h, self.w, out.data_ptr(), s))
         return out
 
     def tags(self, tag_sets, out=None, stream=None):
@@ -131,7 +141,7 @@ class BboxLabelsGPU:
 
 class BoxLists(list):
     """A bbox-weak sub-batch as box lists: items (cids, coords (k, 4), src_size, resized_size,
-    offset), as the reference's prebatch map sees them before _generate_rla. Passed as
+    offset[, flip]), as the reference's prebatch map sees them before _generate_rla. Passed as
     labels['prolabels_per_bbox'], it is rasterised on the device by define_losses."""
 
 

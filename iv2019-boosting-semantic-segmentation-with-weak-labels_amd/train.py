@@ -103,6 +103,15 @@ def add_train_input_pipeline_arguments(argparser):
                                 'and cycled (default 8); 0 = a fresh seeded batch every step')
     argparser.add_argument('--input_seed', type=int, default=0,
                            help='seed of the shuffles and crop offsets (the reference seeds nothing)')
+    # the augmentation call block of the reference's train pipelines (commented out there,
+    # input_cityscapes.py:106-118); device kernels, input_pipelines/augment.py; real-data input only
+    argparser.add_argument('--augment_color', action='store_true',
+                           help='random_color: brightness / saturation / hue / contrast in a random order')
+    argparser.add_argument('--augment_flip', action='store_true',
+                           help='random_flipping: mirror each image (and its labels) with p = 1/2')
+    argparser.add_argument('--augment_scale', type=float, nargs=2, default=None, metavar=('LOW', 'HIGH'),
+                           help='random_scaling of the per-pixel stream with scale_poi = [LOW, HIGH] '
+                                '(the reference: 1.0 2.0)')
 
 
 def train_input_fn(settings):
