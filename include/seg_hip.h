@@ -252,15 +252,23 @@ int seg_bbox_labels_flip(const float* boxes, const int32_t* cids, const int32_t*
                          int W, float* out, void* stream);
 
 /* training augmentation on the device (preprocessing/augmentation_library.py: random_color
- * :359-406, random_flipping :298-321, random_scaling :21-296; random_blur is not built), the call
+ * :359-406, random_blur :408-466, random_flipping :298-321, random_scaling :21-296), the call
  * block the reference's train pipelines hold between the resize and from_0_1_to_m1_1
  * (input_cityscapes.py:106-118). The random draws are the caller's: one record per image, and
  * the kernels are pure functions of (raw input, record). Per image: resize (as
- * seg_prepare_images_crop) -> colour -> flip stage -> scaling -> (x - 0.5) / 0.5.
+ * seg_prepare_images_crop) -> colour -> blur -> flip stage -> scaling -> (x - 0.5) / 0.5.
  *   colour  color_order -1 = none, else the op order 0: B S H C, 1: S B C H, 2: C H B S,
  *           3: H S C B, then clip to [0, 1]. B: x + brightness_delta; S / H: through HSV,
  *           s = clip(s * saturation_factor, 0, 1) / h = frac(h + hue_delta);
  *           C: (x - m) * contrast_factor + m, m = per-channel mean of the image entering the op
+ *   blur    blur.mode 0 = none; 1 median, as cv2.medianBlur on 8-bit data: q = trunc(x * 255),
+ *           per-channel median of the blur.ksize^2 window with replicated borders, q / 255;
+ *           2 bilateral, as cv2.bilateralFilter on float data with sigmaColor = sigmaSpace =
+ *           blur.sigma: taps (i, j) with i^2 + j^2 <= (blur.ksize / 2)^2, reflect-101 borders,
+ *           weight exp(-(i^2 + j^2) / (2 sigma^2)) * exp(-(|dR| + |dG| + |dB|)^2 / (2 sigma^2)),
+ *           weighted mean per channel (the closed form; cv2's interpolated colour-weight table
+ *           is not reproduced). blur.ksize is odd, 3..9. An all-zero blur (what a caller that
+ *           zeroes the former padding words passes) is no blur. Labels are untouched
  *   flip    quantize = 1 (the stage is enabled): the image goes through uint8 (trunc(x * 255.5))
  *           and back (q * (1 / 255)), flipped or not; flip = 1 mirrors image and label in x
  *   scale   scale_mode 0 none; 1 up: crop (sh, sw) at (oy, ox), uint8 round trip, legacy bilinear
@@ -269,6 +277,10 @@ int seg_bbox_labels_flip(const float* boxes, const int32_t* cids, const int32_t*
  *           scalar mean of the resized image (labels: void_cid)
  * A record is SEG_AUG_PARAMS_BYTES = 64 bytes. */
 #define SEG_AUG_PARAMS_BYTES 64
+typedef struct seg_aug_blur {   /* the last 12 bytes of the record */
+  int32_t mode, ksize;
+  float sigma;
+} seg_aug_blur;
 typedef struct seg_aug_params {
   int32_t color_order;
   float brightness_delta, saturation_factor, hue_delta, contrast_factor;
@@ -277,17 +289,19 @@ typedef struct seg_aug_params {
   int32_t sh, sw;
   int32_t oy, ox;
   int32_t void_cid;
-  int32_t reserved[3];   /* pads the record to 64 bytes; ignored */
+  seg_aug_blur blur;
 } seg_aug_params;
 /* The table is passed twice: params_host (host memory) is validated before anything is launched
  * and supplies the host-divided resize scales, params_dev (device memory, the same n records) is
  * what the kernels read. -EINVAL with a seg_last_error text, and no launch, for: a scaled size
  * outside 1..H x 1..W, a crop outside the image, color_order outside -1..3, scale_mode outside
- * 0..2, a window outside the resized image, a workspace smaller than seg_augment_workspace says,
+ * 0..2, blur.mode outside 0..2, with a blur an even blur.ksize or one outside 3..9, for the
+ * bilateral a blur.sigma that is not finite and positive or min(H, W) < blur.ksize / 2 + 1, a window outside the resized image, a workspace smaller than seg_augment_workspace says,
  * out or workspace not 16-byte aligned.
  * seg_augment_images: raw uint8 [n][src_h][src_w][3] + the geometry of seg_prepare_images_crop
  *   (plain resize: resized = H x W, crop 0, 0) -> fp32 [n][H][W][3]. workspace (device) holds the
- *   stage between the colour pass and the geometric pass and the partial sums of the two means;
+ *   stage between the colour pass and the geometric pass (the blur pass moves an image between
+ *   the stage and out, never in place) and the partial sums of the two means;
  *   both means are reduced in a fixed order (no atomics): same inputs, bitwise same output.
  *   With an all-off record the output is bitwise seg_prepare_images_crop's.
  * seg_augment_labels: raw uint8 ids [n][src_h][src_w] + lids2cids as seg_prepare_labels -> one
@@ -307,6 +321,10 @@ int seg_augment_labels(const uint8_t* raw, int n, int src_h, int src_w, int H, i
  * call and stores its four pass times in milliseconds (0 for a skipped pass). Synchronises; not
  * for use while a stream is being captured. */
 int seg_augment_profile(int enable, float* pass_ms);
+/* the blur pass (between colour and down-scale mean) of the same recorded call, in milliseconds;
+ * the empty interval between two events (microseconds) when no image of the call had a blur.
+ * Profiling must be enabled; synchronises. */
+int seg_augment_profile_blur(float* blur_ms);
 
 /* internal tensors for parity tests: "logits", "grad_un", "dzscale", "feat", "dfeat", "z0",
  * "head<h>_out", "head<h>_dout", "pyr<b>_z" (pyramid branch b's BN + ReLU output at its pooled

@@ -18,7 +18,10 @@ struct AugParams {        // 64 bytes, one per image
   int32_t sh, sw;         // up: crop size; down: resized size
   int32_t oy, ox;         // up: crop offset
   int32_t void_cid;       // label fill of the down-scale pad
-  int32_t reserved[3];
+  // seg_aug_params' blur sub-record (mode, ksize, sigma), flat
+  int32_t blur_mode;      // 0 none, 1 median, 2 bilateral
+  int32_t blur_ksize;     // odd, 3..9: the k x k window (median), the disc's diameter (bilateral)
+  float blur_sigma;       // bilateral: sigmaColor = sigmaSpace, on values in [0, 1]
 };
 static_assert(sizeof(AugParams) == 64, "seg_aug_params is 64 bytes");
 
@@ -51,6 +54,27 @@ static inline int aug_validate(const AugParams* p, int n, int H, int W, char* ms
       snprintf(msg, len, "image %d: crop %dx%d at (%d, %d) outside the %dx%d image", i, a.sh, a.sw,
                a.oy, a.ox, H, W);
       return i + 1;
+    }
+    if (a.blur_mode < 0 || a.blur_mode > 2) {
+      snprintf(msg, len, "image %d: blur.mode = %d (0..2)", i, a.blur_mode);
+      return i + 1;
+    }
+    if (a.blur_mode != 0 && (a.blur_ksize < 3 || a.blur_ksize > 9 || a.blur_ksize % 2 == 0)) {
+      snprintf(msg, len, "image %d: blur.ksize = %d (odd, 3..9)", i, a.blur_ksize);
+      return i + 1;
+    }
+    if (a.blur_mode == 2) {
+      // a NaN fails the first comparison, an infinity the second
+      if (!(a.blur_sigma > 0.f) || !(a.blur_sigma <= 3.4028234e38f)) {
+        snprintf(msg, len, "image %d: blur.sigma = %g (finite, > 0)", i, (double)a.blur_sigma);
+        return i + 1;
+      }
+      // reflect-101 reaches blur_ksize / 2 pixels past an edge
+      if ((H < W ? H : W) < a.blur_ksize / 2 + 1) {
+        snprintf(msg, len, "image %d: bilateral blur.ksize = %d needs min(H, W) >= %d, got %dx%d", i,
+                 a.blur_ksize, a.blur_ksize / 2 + 1, H, W);
+        return i + 1;
+      }
     }
   }
   return 0;

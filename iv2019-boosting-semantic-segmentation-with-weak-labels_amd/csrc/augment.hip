@@ -169,7 +169,9 @@ __global__ __launch_bounds__(AG_THREADS) void aug_contrast_mean_kernel(
 }
 
 // pass 2: resize + colour + clip + the flip stage's quantisation; an image with no geometry
-// is centred and finished here, the others go to the stage un-centred
+// is centred and finished here, the others go to the stage un-centred. An image with blur
+// leaves quantisation and centring to the blur pass and goes to the buffer that pass reads:
+// out when geometry follows (the blur then fills the stage), else the stage
 __global__ __launch_bounds__(AG_THREADS) void aug_colour_kernel(
     const uint8_t* __restrict__ raw, AugArgs g, const AugParams* __restrict__ prm,
     const float* __restrict__ part, float* __restrict__ stage, float* __restrict__ out) {
@@ -178,6 +180,7 @@ __global__ __launch_bounds__(AG_THREADS) void aug_colour_kernel(
   const AugParams a = prm[img];
   const long npix = (long)g.H * g.W;
   const bool geom = a.flip != 0 || a.scale_mode != 0;
+  const bool blur = a.blur_mode != 0;
   const bool colour = a.color_order >= 0;
   const unsigned seq = colour ? colour_seq(a.color_order) : 0u;
   float mean[3] = {0.f, 0.f, 0.f};
@@ -202,18 +205,173 @@ __global__ __launch_bounds__(AG_THREADS) void aug_colour_kernel(
 #pragma unroll
         for (int i = 0; i < 3; ++i) c[i] = clip01(c[i]);
       }
-      if (a.quantize) {
+      if (a.quantize && !blur) {
 #pragma unroll
         for (int i = 0; i < 3; ++i) c[i] = quant(c[i]);
       }
-      if (!geom) {
+      if (!geom && !blur) {
 #pragma unroll
         for (int i = 0; i < 3; ++i) c[i] = centre(c[i]);
       }
     }
     v[3 * k] = c[0]; v[3 * k + 1] = c[1]; v[3 * k + 2] = c[2];
   }
-  store_px((geom ? stage : out) + (size_t)img * npix * 3, p0, npix, (npix % AG_PX) == 0, v);
+  store_px((geom != blur ? stage : out) + (size_t)img * npix * 3, p0, npix, (npix % AG_PX) == 0, v);
+}
+
+// ---- pass 2b: random_blur (augment.h) -------------------------------------------------------
+// One block per BL_TH x BL_TW output tile: the tile and its K / 2 halo are staged in LDS with the
+// border rule applied (every staged coordinate is clamped into the image, so a ragged tile reads
+// nothing outside it), then each thread finishes BL_PX pixels from LDS alone.
+constexpr int BL_TW = 64, BL_TH = 32;
+constexpr int BL_PX = BL_TW * BL_TH / AG_THREADS;
+constexpr int BL_KMAX = 9;
+constexpr int BL_LDS_FLOATS = (BL_TH + BL_KMAX - 1) * (BL_TW + BL_KMAX - 1) * 3;
+
+// where the tile's results go: the flip stage's round trip, and the centring of an image that no
+// geometry pass follows
+__device__ __forceinline__ void blur_store(float* dst, int W, int y, int x, float c[3], bool q,
+                                           bool ctr) {
+  float* o = dst + ((size_t)y * W + x) * 3;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    float v = c[i];
+    if (q) v = quant(v);
+    if (ctr) v = centre(v);
+    o[i] = v;
+  }
+}
+
+// cv2.medianBlur on 8-bit data: q = trunc(x * 255), per-channel median of the K x K window with
+// replicated borders, q_med / 255. A staged pixel is one word of three 10-bit fields, each the
+// channel's byte with bit 9 set. The median is built most significant bit first: candidate
+// t = m | bit is kept when at least N / 2 + 1 window values are >= t, and (field - t) keeps its
+// bit 9 exactly when value >= t (512 + v - t >= 257, so no borrow crosses a field), so one
+// subtract, shift, mask and add per window word counts all three channels. Exact.
+template <int K>
+__device__ __forceinline__ void blur_median_tile(const float* src, float* dst, int H, int W, int y0,
+                                                 int x0, bool q, bool ctr, uint32_t* lds) {
+  constexpr int R = K / 2, SW = BL_TW + 2 * R, SH = BL_TH + 2 * R, N = K * K;
+  constexpr uint32_t LOW = 1u | (1u << 10) | (1u << 20), GUARD = LOW << 9;
+  for (int e = threadIdx.x; e < SH * SW; e += AG_THREADS) {
+    const int sy = e / SW, sx = e - sy * SW;
+    const int gy = min(max(y0 - R + sy, 0), H - 1), gx = min(max(x0 - R + sx, 0), W - 1);
+    const float* p = src + ((size_t)gy * W + gx) * 3;
+    const uint32_t r = min((uint32_t)(p[0] * 255.f), 255u), g = min((uint32_t)(p[1] * 255.f), 255u),
+                   b = min((uint32_t)(p[2] * 255.f), 255u);
+    lds[e] = r | (g << 10) | (b << 20) | GUARD;
+  }
+  __syncthreads();
+#pragma unroll 1
+  for (int i = 0; i < BL_PX; ++i) {
+    const int e = threadIdx.x + i * AG_THREADS;
+    const int ly = e / BL_TW, lx = e % BL_TW;
+    if (y0 + ly >= H || x0 + lx >= W) continue;
+    uint32_t w[N];
+#pragma unroll
+    for (int dy = 0; dy < K; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < K; ++dx) w[dy * K + dx] = lds[(ly + dy) * SW + lx + dx];
+    uint32_t m = 0;
+#pragma unroll
+    for (int bit = 7; bit >= 0; --bit) {
+      const uint32_t t = m | (LOW << bit);
+      uint32_t ge = 0;
+#pragma unroll
+      for (int k = 0; k < N; ++k) ge += ((w[k] - t) >> 9) & LOW;
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        if (((ge >> (10 * c)) & 0x3ffu) >= (uint32_t)(N / 2 + 1)) m |= (1u << bit) << (10 * c);
+    }
+    float c[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c[k] = (float)((m >> (10 * k)) & 0xffu) / 255.f;
+    blur_store(dst, W, y0 + ly, x0 + lx, c, q, ctr);
+  }
+}
+
+__device__ __forceinline__ int reflect101(int g, int n) {   // n >= K / 2 + 1 (aug_validate)
+  g = g < 0 ? -g : g;
+  g = g >= n ? 2 * n - 2 - g : g;
+  return min(max(g, 0), n - 1);   // only positions of a ragged tile that no kept output reads
+}
+
+// cv2.bilateralFilter's float path in closed form: taps on the disc i^2 + j^2 <= R^2, borders
+// reflect-101, weight exp(coef * (i^2 + j^2)) * exp(coef * (|dR| + |dG| + |dB|)^2) with
+// coef = -0.5 / sigma^2, weighted mean per channel. Taps are summed row by row.
+template <int K>
+__device__ __forceinline__ void blur_bilateral_tile(const float* src, float* dst, int H, int W,
+                                                    int y0, int x0, float sigma, bool q, bool ctr,
+                                                    float* lds) {
+  constexpr int R = K / 2, SW = BL_TW + 2 * R, SH = BL_TH + 2 * R;
+  for (int e = threadIdx.x; e < SH * SW * 3; e += AG_THREADS) {
+    const int sy = e / (SW * 3), rem = e - sy * (SW * 3);
+    const int sx = rem / 3, c = rem - sx * 3;
+    const int gy = reflect101(y0 - R + sy, H), gx = reflect101(x0 - R + sx, W);
+    lds[e] = src[((size_t)gy * W + gx) * 3 + c];
+  }
+  __syncthreads();
+  // a sigma whose square underflows would give 0 * -inf at the centre tap
+  const float coef = fmaxf(-0.5f / (sigma * sigma), -3.4028234e38f);
+  float sp[R * R + 1];
+#pragma unroll
+  for (int d = 0; d <= R * R; ++d) sp[d] = expf((float)d * coef);
+#pragma unroll 1
+  for (int i = 0; i < BL_PX; ++i) {
+    const int e = threadIdx.x + i * AG_THREADS;
+    const int ly = e / BL_TW, lx = e % BL_TW;
+    if (y0 + ly >= H || x0 + lx >= W) continue;
+    const float* ctrp = lds + ((ly + R) * SW + lx + R) * 3;
+    const float c0 = ctrp[0], c1 = ctrp[1], c2 = ctrp[2];
+    float acc[3] = {0.f, 0.f, 0.f}, sum = 0.f;
+#pragma unroll
+    for (int dy = -R; dy <= R; ++dy)
+#pragma unroll
+      for (int dx = -R; dx <= R; ++dx) {
+        if (dy * dy + dx * dx > R * R) continue;
+        const float* p = ctrp + (dy * SW + dx) * 3;
+        const float p0 = p[0], p1 = p[1], p2 = p[2];
+        const float d = (fabsf(p0 - c0) + fabsf(p1 - c1)) + fabsf(p2 - c2);
+        const float wgt = sp[dy * dy + dx * dx] * expf((d * d) * coef);
+        acc[0] += p0 * wgt; acc[1] += p1 * wgt; acc[2] += p2 * wgt;
+        sum += wgt;
+      }
+    float c[3] = {acc[0] / sum, acc[1] / sum, acc[2] / sum};
+    blur_store(dst, W, y0 + ly, x0 + lx, c, q, ctr);
+  }
+}
+
+// Reads the buffer the colour pass wrote for the image and writes the other one: stage -> out
+// (finished: quantised, centred) without geometry, out -> stage (quantised) with it.
+__global__ __launch_bounds__(AG_THREADS) void aug_blur_kernel(float* stage, float* out, int H, int W,
+                                                              int tiles_x,
+                                                              const AugParams* __restrict__ prm) {
+  __shared__ float lds[BL_LDS_FLOATS];
+  const int img = blockIdx.y;
+  const AugParams a = prm[img];
+  if (a.blur_mode == 0) return;
+  const bool geom = a.flip != 0 || a.scale_mode != 0;
+  const size_t off = (size_t)img * H * W * 3;
+  const float* src = (geom ? out : stage) + off;
+  float* dst = (geom ? stage : out) + off;
+  const int y0 = (int)(blockIdx.x / tiles_x) * BL_TH, x0 = (int)(blockIdx.x % tiles_x) * BL_TW;
+  const bool q = a.quantize != 0, ctr = !geom;
+  if (a.blur_mode == 1) {
+    uint32_t* l = (uint32_t*)lds;
+    switch (a.blur_ksize) {   // uniform per block
+      case 3: blur_median_tile<3>(src, dst, H, W, y0, x0, q, ctr, l); break;
+      case 5: blur_median_tile<5>(src, dst, H, W, y0, x0, q, ctr, l); break;
+      case 7: blur_median_tile<7>(src, dst, H, W, y0, x0, q, ctr, l); break;
+      default: blur_median_tile<9>(src, dst, H, W, y0, x0, q, ctr, l); break;
+    }
+  } else {
+    switch (a.blur_ksize) {
+      case 3: blur_bilateral_tile<3>(src, dst, H, W, y0, x0, a.blur_sigma, q, ctr, lds); break;
+      case 5: blur_bilateral_tile<5>(src, dst, H, W, y0, x0, a.blur_sigma, q, ctr, lds); break;
+      case 7: blur_bilateral_tile<7>(src, dst, H, W, y0, x0, a.blur_sigma, q, ctr, lds); break;
+      default: blur_bilateral_tile<9>(src, dst, H, W, y0, x0, a.blur_sigma, q, ctr, lds); break;
+    }
+  }
 }
 
 // the staged image after the flip: pixel (y, x) of the flip stage's output
@@ -381,14 +539,16 @@ AugScales chunk_scales(const AugParams* host, int nc, int H, int W) {
   return sc;
 }
 
-// pass timing (seg_augment_profile): events around the four passes of a call's first chunk
+// pass timing (seg_augment_profile[_blur]): events around the passes of a call's first chunk, in
+// launch order: contrast mean, colour, blur, down-scale mean, geometry
 bool g_prof = false;
-hipEvent_t g_ev[5] = {};
+constexpr int AG_EVENTS = 6;
+hipEvent_t g_ev[AG_EVENTS] = {};
 
 }  // namespace
 
 hipError_t aug_profile_enable(bool on) {
-  for (int i = 0; i < 5 && on && !g_ev[i]; ++i) {
+  for (int i = 0; i < AG_EVENTS && on && !g_ev[i]; ++i) {
     const hipError_t e = hipEventCreate(&g_ev[i]);
     if (e != hipSuccess) return e;
   }
@@ -398,9 +558,17 @@ hipError_t aug_profile_enable(bool on) {
 
 hipError_t aug_profile_read(float ms[4]) {
   if (!g_ev[0]) return hipErrorNotReady;
-  hipError_t e = hipEventSynchronize(g_ev[4]);
-  for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipEventElapsedTime(&ms[i], g_ev[i], g_ev[i + 1]);
+  hipError_t e = hipEventSynchronize(g_ev[AG_EVENTS - 1]);
+  const int first[4] = {0, 1, 3, 4};   // the blur pass sits between events 2 and 3
+  for (int i = 0; i < 4 && e == hipSuccess; ++i)
+    e = hipEventElapsedTime(&ms[i], g_ev[first[i]], g_ev[first[i] + 1]);
   return e;
+}
+
+hipError_t aug_profile_read_blur(float* ms) {
+  if (!g_ev[0]) return hipErrorNotReady;
+  const hipError_t e = hipEventSynchronize(g_ev[AG_EVENTS - 1]);
+  return e == hipSuccess ? hipEventElapsedTime(ms, g_ev[2], g_ev[3]) : e;
 }
 
 // [stage n * H * W * 3 floats][contrast partials n * AUG_PARTS * 4][down partials n * AUG_PARTS]
@@ -424,12 +592,13 @@ hipError_t launch_augment_images(const uint8_t* raw, int n, const AugResize& r, 
   const unsigned gx = (unsigned)ceil_div((long)npix, (long)AG_THREADS * AG_PX);
   for (int b0 = 0; b0 < n; b0 += AUG_MAX_CHUNK) {
     const int nc = std::min(n - b0, AUG_MAX_CHUNK);
-    bool colour = false, geom = false, down = false;
+    bool colour = false, geom = false, down = false, blur = false;
     for (int i = 0; i < nc; ++i) {
       const AugParams& a = host[b0 + i];
       colour |= a.color_order >= 0;
       geom |= a.flip != 0 || a.scale_mode != 0;
       down |= a.scale_mode == 2;
+      blur |= a.blur_mode != 0;
     }
     const AugScales sc = chunk_scales(host + b0, nc, H, W);
     const uint8_t* raw_c = raw + (size_t)b0 * r.Hr * r.Wr * 3;
@@ -447,14 +616,20 @@ hipError_t launch_augment_images(const uint8_t* raw, int n, const AugResize& r, 
     hipLaunchKernelGGL(aug_colour_kernel, dim3(gx, nc), dim3(AG_THREADS), 0, s, raw_c, g, prm, p1,
                        stage_c, out_c);
     if (prof) (void)hipEventRecord(g_ev[2], s);
+    if (blur) {
+      const int tx = ceil_div(W, BL_TW), ty = ceil_div(H, BL_TH);
+      hipLaunchKernelGGL(aug_blur_kernel, dim3((unsigned)(tx * ty), nc), dim3(AG_THREADS), 0, s,
+                         stage_c, out_c, H, W, tx, prm);
+    }
+    if (prof) (void)hipEventRecord(g_ev[3], s);
     if (down)
       hipLaunchKernelGGL(aug_down_mean_kernel, dim3(AUG_PARTS, nc), dim3(AG_THREADS), 0, s,
                          stage_c, H, W, prm, sc, p2);
-    if (prof) (void)hipEventRecord(g_ev[3], s);
+    if (prof) (void)hipEventRecord(g_ev[4], s);
     if (geom)
       hipLaunchKernelGGL(aug_geometry_kernel, dim3(gx, nc), dim3(AG_THREADS), 0, s, stage_c, H, W,
                          prm, sc, p2, out_c);
-    if (prof) (void)hipEventRecord(g_ev[4], s);
+    if (prof) (void)hipEventRecord(g_ev[5], s);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }

@@ -2381,6 +2381,10 @@ static LidMap lid_map(const int32_t* lids2cids, int n_lids) {
 
 static_assert(sizeof(seg_aug_params) == sizeof(AugParams) && sizeof(AugParams) == SEG_AUG_PARAMS_BYTES,
               "seg_aug_params layout");
+static_assert(offsetof(seg_aug_params, blur) == offsetof(AugParams, blur_mode) &&
+              offsetof(seg_aug_params, blur) + offsetof(seg_aug_blur, ksize) == offsetof(AugParams, blur_ksize) &&
+              offsetof(seg_aug_params, blur) + offsetof(seg_aug_blur, sigma) == offsetof(AugParams, blur_sigma) &&
+              offsetof(AugParams, blur_mode) == 52, "seg_aug_params blur words");
 
 // the shared checks of the two augmentation entries: the table is validated from the caller's
 // host copy before anything is launched
@@ -2405,6 +2409,12 @@ int seg_augment_profile(int enable, float* pass_ms) {
   hipError_t e = aug_profile_enable(enable != 0);
   if (e == hipSuccess && pass_ms) e = aug_profile_read(pass_ms);
   return e == hipSuccess ? 0 : hip_fail(nullptr, e, "seg_augment_profile");
+}
+
+int seg_augment_profile_blur(float* blur_ms) {
+  if (!blur_ms) return set_err(nullptr, -EINVAL, "seg_augment_profile_blur: bad arguments");
+  const hipError_t e = aug_profile_read_blur(blur_ms);
+  return e == hipSuccess ? 0 : hip_fail(nullptr, e, "seg_augment_profile_blur");
 }
 
 int seg_augment_images(const uint8_t* raw, int n, int src_h, int src_w, int resized_h,

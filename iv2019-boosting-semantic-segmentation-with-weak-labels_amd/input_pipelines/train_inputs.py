@@ -37,17 +37,19 @@ selection runs in order on the calling thread, the PNG / JPEG decodes of the nex
 GIL while it decodes), and each batch's uploads + device preprocessing are issued when the
 training loop takes it.
 
-Augmentation (``--augment_color``, ``--augment_flip``, ``--augment_scale LOW HIGH``; all off by
-default: input_pipelines/augment.py). With a flag on, every stream's images go through
-``seg_augment_images`` instead of ``seg_prepare_images[_crop]``: the per-pixel stream gets
-colour + flip + scaling (its labels through ``seg_augment_labels``), the bbox and tag streams
-colour + flip only (their dense labels are float multinomials, which random_scaling asserts
-against, augmentation_library.py:97, and they already random-crop an aspect-preserving
-resize). A flipped bbox image carries its flag as a 6th element of its ``BoxLists`` item and
+Augmentation (``--augment_color``, ``--augment_blur``, ``--augment_flip``,
+``--augment_scale LOW HIGH``; all off by default: input_pipelines/augment.py). With a flag on,
+every stream's images go through ``seg_augment_images`` instead of
+``seg_prepare_images[_crop]``: the per-pixel stream gets colour + blur + flip + scaling (its
+labels through ``seg_augment_labels``), the bbox and tag streams colour + blur + flip only
+(their dense labels are float multinomials, which random_scaling asserts against,
+augmentation_library.py:97, and they already random-crop an aspect-preserving resize; blur
+changes images only). A flipped bbox image carries its flag as a 6th element of its ``BoxLists`` item and
 is rasterised mirrored (``seg_bbox_labels_flip``); tag sets are flip-invariant. The draws come
 from a third generator per stream, ``default_rng([seed, s, rank, 2])``, so the shuffles and
-crop offsets are what they are without augmentation; with the flags off no augmentation
-kernel is launched and the batches are unchanged.
+crop offsets are what they are without augmentation; the blur draws come from a fourth,
+``default_rng([seed, s, rank, 3])``, so ``--augment_blur`` moves no colour, flip or scaling
+draw. With the flags off no augmentation kernel is launched and the batches are unchanged.
 """
 from __future__ import annotations
 
@@ -220,11 +222,16 @@ def heterogeneous_train_input(config, params) -> Callable:
     lids2cids = list(params.training_problem_def['lids2cids'])
     a_color = bool(getattr(params, 'augment_color', False))
     a_flip = bool(getattr(params, 'augment_flip', False))
+    a_blur = bool(getattr(params, 'augment_blur', False))
     a_scale = getattr(params, 'augment_scale', None)
     a_scale = None if a_scale is None or tuple(a_scale) == (1.0, 1.0) else tuple(a_scale)
-    aug_pp = a_color or a_flip or a_scale is not None      # per-pixel: colour + flip + scaling
-    aug_weak = a_color or a_flip                           # bbox / tag: colour + flip
+    aug_pp = a_color or a_blur or a_flip or a_scale is not None   # per-pixel: all four stages
+    aug_weak = a_color or a_blur or a_flip                 # bbox / tag: colour + blur + flip
     aug = [np.random.default_rng([seed, s, rank, 2]) for s in range(3)]   # augmentation draws
+    aug_blur = [np.random.default_rng([seed, s, rank, 3]) for s in range(3)] if a_blur else [None] * 3
+    if a_blur:
+        from input_pipelines.augment import blur_draw_range
+        blur_draw_range(H, W)   # a network size the blur kernels do not cover fails here
     void_cid = max(lids2cids) + 1
     pp = PerPixelStream(params.tfrecords_path_per_pixel, rngs[0], rank, world) if nb[0] else None
     if nb[1] and not (params.bboxes_index_path and params.bboxes_images_dir):
@@ -265,7 +272,8 @@ def heterogeneous_train_input(config, params) -> Callable:
                 ex = [f.result() for f in job['pp']]
                 same = len({e[0].shape for e in ex}) == 1
                 ap = draw_params(aug[0], len(ex), H, W, color=a_color, flip=a_flip,
-                                 scale_poi=a_scale, void_cid=void_cid) if aug_pp else None
+                                 scale_poi=a_scale, void_cid=void_cid, blur=a_blur,
+                                 blur_rng=aug_blur[0]) if aug_pp else None
                 if same:   # one upload + one launch for the sub-batch
                     raw_i = torch.from_numpy(np.stack([e[0] for e in ex])).pin_memory().to(dev, non_blocking=True)
                     raw_l = torch.from_numpy(np.stack([e[1] for e in ex])).pin_memory().to(dev, non_blocking=True)
@@ -287,8 +295,10 @@ def heterogeneous_train_input(config, params) -> Callable:
                 if kind not in job:
                     continue
                 g = geom[1] if kind == 'bbox' else geom[2]
-                ap = draw_params(aug[1 if kind == 'bbox' else 2], len(job[kind]), H, W,
-                                 color=a_color, flip=a_flip, void_cid=void_cid) if aug_weak else None
+                s = 1 if kind == 'bbox' else 2
+                ap = draw_params(aug[s], len(job[kind]), H, W, color=a_color, flip=a_flip,
+                                 void_cid=void_cid, blur=a_blur,
+                                 blur_rng=aug_blur[s]) if aug_weak else None
                 for i, (iid, ann, fut) in enumerate(job[kind]):
                     im = fut.result()
                     src = im.shape[:2]

@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = [
     "seg_counter",
     "seg_crc32c", "seg_prepare_images", "seg_prepare_labels", "seg_prepare_images_crop",
     "seg_bbox_labels_flip", "seg_augment_workspace", "seg_augment_images", "seg_augment_labels", "seg_augment_profile",
+    "seg_augment_profile_blur",
 ]
 
 # int (*seg_allreduce_fn)(void* user, float* buf, int64_t n, void* stream)
@@ -127,6 +128,7 @@ def _load():
         "seg_augment_labels": (ip, [vp, ip, ip, ip, ip, ip, ctypes.POINTER(ctypes.c_int32), ip,
                                     vp, vp, vp, vp]),
         "seg_augment_profile": (ip, [ip, ctypes.POINTER(ctypes.c_float)]),
+        "seg_augment_profile_blur": (ip, [ctypes.POINTER(ctypes.c_float)]),
         "seg_crc32c": (ctypes.c_uint32, [ctypes.c_uint32, vp, ctypes.c_size_t]),
         "seg_predict": (ip, [vp, ctypes.POINTER(ctypes.c_int32), ip, ip, ip, ip, vp, vp]),
         "seg_full_predictions": (ip, [vp, vp, vp, vp, vp, vp]),

@@ -107,6 +107,9 @@ def add_train_input_pipeline_arguments(argparser):
     # input_cityscapes.py:106-118); device kernels, input_pipelines/augment.py; real-data input only
     argparser.add_argument('--augment_color', action='store_true',
                            help='random_color: brightness / saturation / hue / contrast in a random order')
+    argparser.add_argument('--augment_blur', action='store_true',
+                           help='random_blur: per batch a k x k median, a bilateral filter or nothing '
+                                '(p = 1/4, 1/4, 1/2), k drawn per image from the network size')
     argparser.add_argument('--augment_flip', action='store_true',
                            help='random_flipping: mirror each image (and its labels) with p = 1/2')
     argparser.add_argument('--augment_scale', type=float, nargs=2, default=None, metavar=('LOW', 'HIGH'),

@@ -12,7 +12,14 @@ compulsory bytes (every operand read / written once) and GB/s. Times are medians
 after WARM warm-up calls per row. The added time is also given as a share of the 34.91 ms C2
 step of BENCH_r06.json.
 
-    python tools/aug_table.py > profiles/augment_table.txt"""
+With --blur: the blur pass (seg_augment_profile_blur's device events) on the same C2 batch for
+the median and the bilateral filter at k = 3, 5, 7, 9, beside its HBM floor (12 B read + 12 B
+written per pixel at the COPY_TBS copy rate of DESIGN 0a'), and the whole augmentation with all
+four stages on, as milliseconds and as a share of BLUR_STEP_MS (a plain bench.py run of the
+commit before the blur, same session).
+
+    python tools/aug_table.py > profiles/augment_table.txt
+    python tools/aug_table.py --blur > profiles/augment_blur_table.txt"""
 import ctypes
 import os
 import sys
@@ -24,6 +31,8 @@ sys.path[:0] = [REPO, os.path.join(REPO, "iv2019-boosting-semantic-segmentation-
 
 WARM, REPS = 5, 30
 STEP_MS = 34.91          # BENCH_r06.json ms_per_step (C2)
+BLUR_STEP_MS = 34.66     # bench.py --steps 20 --warmup 5 of the parent commit: 34.69 / 34.67 / 34.62
+COPY_TBS = 6.29          # DESIGN 0a': the copy ceiling
 L2C = [-1] * 7 + list(range(19)) + [-1] * 8
 PASSES = ("contrast mean", "colour", "down mean", "geometry")
 
@@ -133,11 +142,66 @@ def table(title, n, src, H, W, resized, offset, weak, torch, dev):
     print()
 
 
+def blur_table(n, H, W, torch, dev):
+    """The blur pass alone per (filter, k), then all four stages on."""
+    from input_pipelines.augment import augment_images, augment_labels, blur_draw_range
+    from seg_hip import LIB, check
+    g = torch.Generator().manual_seed(1)
+    raw = torch.randint(0, 256, (n, H, W, 3), dtype=torch.uint8, generator=g).to(dev)
+    lab = torch.randint(0, 34, (n, H, W), dtype=torch.uint8, generator=g).to(dev)
+    sigma = blur_draw_range(H, W)[1]
+    nbytes = n * H * W * 24
+    floor = nbytes / (COPY_TBS * 1e9)     # ms
+    print(f"== blur pass, C2 per-pixel batch: n = {n}, {H}x{W}, sigma = {sigma:g}; compulsory "
+          f"{nbytes / 1e6:.2f} MB (12 B read + 12 B written per pixel) = {floor:.4f} ms at "
+          f"{COPY_TBS} TB/s")
+    print(f"{'filter':<10} {'k':>2} {'blur ms':>9} {'x floor':>8} {'GB/s':>7} {'% step':>7} "
+          f"{'images (call) ms':>17}")
+
+    def blur_ms(p):
+        check(LIB.seg_augment_profile(1, None))
+        per = []
+        for _ in range(WARM + REPS):
+            augment_images(raw, p, H, W)
+            ms = ctypes.c_float(0)
+            check(LIB.seg_augment_profile_blur(ctypes.byref(ms)))
+            per.append(ms.value)
+        check(LIB.seg_augment_profile(0, None))
+        return float(np.median(per[WARM:]))
+    for mode, name in ((1, "median"), (2, "bilateral")):
+        for k in (3, 5, 7, 9):
+            p = records("off", n, H, W)
+            p["blur"]["mode"], p["blur"]["ksize"], p["blur"]["sigma"] = mode, k, sigma if mode == 2 else 0
+            ms = blur_ms(p)
+            call = median_ms(lambda: augment_images(raw, p, H, W), torch)
+            print(f"{name:<10} {k:>2} {ms:9.4f} {ms / floor:8.2f} {nbytes / ms / 1e6:7.0f} "
+                  f"{100 * ms / BLUR_STEP_MS:7.2f} {call:17.4f}")
+    print()
+    print(f"== all four stages on (colour, blur, flip, half the images scaled up, half down), "
+          f"images + labels; share of the {BLUR_STEP_MS} ms C2 step")
+    print(f"{'blur':<14} {'blur ms':>9} {'images ms':>10} {'labels ms':>10} {'total ms':>9} {'% step':>7}")
+    for mode, name, k in ((0, "none", 0), (1, "median", 3), (1, "median", 9), (2, "bilateral", 3),
+                          (2, "bilateral", 9)):
+        p = records("all", n, H, W)
+        p["blur"]["mode"], p["blur"]["ksize"], p["blur"]["sigma"] = mode, k, sigma if mode == 2 else 0
+        ms = blur_ms(p)
+        ti = median_ms(lambda: augment_images(raw, p, H, W), torch)
+        tl = median_ms(lambda: augment_labels(lab, p, H, W, L2C), torch)
+        print(f"{(name + (f' k={k}' if k else '')):<14} {ms:9.4f} {ti:10.4f} {tl:10.4f} {ti + tl:9.4f} "
+              f"{100 * (ti + tl) / BLUR_STEP_MS:7.2f}")
+
+
 def main():
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("aug_table.py measures on the GPU; none is visible")
     dev = torch.device("cuda", 0)
+    if "--blur" in sys.argv[1:]:
+        print(f"# {torch.cuda.get_device_name(0)}; medians of {REPS} calls after {WARM} warm-up "
+              "calls; 'blur ms' is device events around the blur kernel, the call columns include "
+              "the wrapper (parameter upload, workspace and output allocation)")
+        blur_table(4, 1024, 2048, torch, dev)
+        return
     print(f"# {torch.cuda.get_device_name(0)}; medians of {REPS} calls after {WARM} warm-up calls; "
           "'images (call)' and 'labels' include the wrapper (parameter upload, workspace and "
           "output allocation), the pass rows are device events around the kernels")
