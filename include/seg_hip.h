@@ -138,8 +138,38 @@ int seg_set_lbf(seg_ctx* ctx, int on);
  * gradients by linearity (seg_set_lbf);
  * "loss_yf_launches" = seg_loss calls whose loss head ran the y-first kernel (the full-res
  *   columns of every block fit one 256-thread chunk: the 512 x 1024 and 1024 x 2048 shapes).
+ * "bootstrap_launches" = seg_loss calls that ran the bootstrapped l1 loss (seg_set_bootstrap):
+ *   loss map + threshold select + gated loss head.
  * -ENOENT for an unknown name. */
 int seg_counter(seg_ctx* ctx, const char* name, int64_t* value);
+
+/* Bootstrapped per-pixel l1 loss, the reference's --bootstrapping_percentage ("Percentage of
+ * pixels to bootstrap while computing the loss. -1 disables bootstrapping. Set it closer to 100
+ * the more unlabeled pixels a dataset has."). The reference accepts the flag but its published
+ * tree ships no loss code behind it, so the semantics are fixed here: online hard-pixel
+ * bootstrapping of the l1 loss, per context (each replica selects over its own sub-batch).
+ *   p = percentage: p <= 0 off (later seg_loss calls launch exactly what they launch without
+ *     this call); 1..100 on; p > 100 returns -EINVAL and seg_last_error names the flag. With
+ *     nb_pp == 0 the call is accepted and does nothing.
+ *   m [nb_pp][H][W] f32, the l1 loss map: the l1 sparse softmax cross-entropy of the upsampled
+ *     l1 logits of the strong images where the l1 weight is 1 (l1 label <= l1_wmax), exactly
+ *     +0.0f where it is 0. Every entry is a finite float >= +0, so bit patterns order as values.
+ *   M = nb_pp * H * W (every pixel, labelled or not), K = max(1, p * M / 100) in 64-bit integers,
+ *     tau = the K-th largest of the M entries of m.
+ *   A pixel is selected iff its l1 weight is 1 and m >= tau: ties at tau are all selected (the
+ *     selected count may exceed K), no ordering by index. The weight is read from the stored m.
+ *   l1_segmentation = sum of the per-pixel loss over the selected pixels / their count (0 if
+ *     none); n1 of seg_outputs is the selected count; the strong images' l1 channels get a
+ *     gradient only at selected pixels, scaled by the new 1 / n1. Both l2 terms, the weak-label
+ *     gate, the decisions, seg = l1 + 0.1 (l2v + l2h), regularisation and loss scaling are
+ *     unchanged; EVAL and PREDICT never see it.
+ *   p = 100, or fewer than K positive entries (tau = 0), selects every weighted pixel: the
+ *     outputs are bitwise those of the off path.
+ * seg_loss then runs: map pass -> exact radix select of tau (three digit passes of 11 + 11 + 10
+ * bits on the float bits, integer histograms, no host synchronisation, no float atomics, bitwise
+ * reproducible) -> the gated loss head. The map and the select's workspace are allocated by the
+ * first enabling call (outside a step) and freed by seg_destroy. */
+int seg_set_bootstrap(seg_ctx* ctx, int percentage);
 
 /* outputs ------------------------------------------------------------------------------
  * losses: device float[10] = {segmentation, l1, l2_vehicle, l2_human, n1, n2v, n2h,
@@ -329,7 +359,8 @@ int seg_augment_profile_blur(float* blur_ms);
 /* internal tensors for parity tests: "logits", "grad_un", "dzscale", "feat", "dfeat", "z0",
  * "head<h>_out", "head<h>_dout", "pyr<b>_z" (pyramid branch b's BN + ReLU output at its pooled
  * resolution), "conv<i>_x" (input of the last forward), "conv<i>_y", "conv<i>_dy" (i =
- * creation index).
+ * creation index); after seg_set_bootstrap enabled it once: "l1_loss_map" ([nb_pp, H, W, 1] f32)
+ * and "bootstrap_tau" (one float) of the last bootstrapped seg_loss.
  * dims = N, H, W, C; ld = pixel stride; dtype = SEG_DTYPE_* of the storage */
 int seg_debug_tensor(seg_ctx* ctx, const char* name, void** ptr, int* dims, int* ld, int* dtype);
 
@@ -381,6 +412,12 @@ int seg_op_conv_dgrad_fused(int dtype, const void* dy, int N, int H, int W, int 
                             const void* r1, int ldr1, const void* r2, int ldr2, const void* dy2,
                             int Co2, int lddy2, const void* wt2, const uint8_t* omask,
                             void* stream);
+/* the threshold select of seg_set_bootstrap on any device array of n finite floats >= +0 (a set
+ * sign bit, -0.0f included, is outside the contract): *tau_out = the k-th largest entry,
+ * *n_ge_out = the count of entries >= tau (both host pointers; the call synchronises `stream`
+ * and allocates its own workspace). -EINVAL for k < 1, k > n or n > 2^31 - 1. */
+int seg_op_bootstrap_threshold(const float* map, int64_t n, int64_t k, float* tau_out,
+                               int64_t* n_ge_out, void* stream);
 
 #ifdef __cplusplus
 }

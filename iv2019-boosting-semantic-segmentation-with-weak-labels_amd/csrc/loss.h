@@ -31,6 +31,10 @@ struct LossArgs {
   float* part;             // [nblocks][8] partial sums {S1,S2v,S2h,n1,n2v,n2h}
   int* decisions;          // optional [N][H][W] fused decisions
   int* l1_decisions;       // optional [N][H][W]
+  // bootstrapped l1 loss (seg_set_bootstrap), both set or both null: the strong images' l1
+  // weight becomes (label valid && l1_map[pixel] >= *tau), read from the stored map
+  const float* l1_map;     // optional [npp][H][W] per-pixel l1 loss (launch_l1_loss_map)
+  const float* tau;        // optional device scalar: the K-th largest entry of l1_map
 };
 
 // EVAL / PREDICT decisions (define_estimator_hierarchical.py:161-194,215-232): per output
@@ -66,6 +70,10 @@ int loss_head_blocks(int N, int Hl, int Wl);
 hipError_t launch_eval_decisions(const EvalArgs& a, const LossTables& t, hipStream_t s);
 hipError_t launch_full_predictions(const FullPredArgs& a, const LossTables& t, hipStream_t s);
 hipError_t launch_loss_head(const LossArgs& a, const LossTables& t, hipStream_t s);
+// map[npp][H][W] = the strong images' l1 sparse softmax-CE of the upsampled l1 logits (the loss
+// head's own arithmetic) where the l1 weight is 1, +0.0f where it is 0; every entry is a finite
+// float >= +0, so its bit pattern orders as the value does (bootstrap.h selects on the bits)
+hipError_t launch_l1_loss_map(const LossArgs& a, const LossTables& t, float* map, hipStream_t s);
 // true when launch_loss_head takes the y-first kernel for this geometry (Cityscapes tables)
 bool loss_head_yf(int W, int Wl);
 // out[0..9] = {seg, l1, l2v, l2h, n1, n2v, n2h, f1, f2v, f2h}; dzscale[ldl] per-channel

@@ -59,7 +59,12 @@ __device__ int first_with_lo_ge(int target, int n_in, int n_out) {
 // registers, and the x-transpose reduction into the owned columns runs once per owned row at the
 // end instead of once per full-resolution row (~32 LDS passes and barrier pairs per block). The
 // same products, summed h-then-w instead of w-then-h.
-template <int C1, int C2, int C3, int YF = 0>
+//
+// BS (bootstrapped l1 loss, seg_set_bootstrap): a strong pixel's l1 weight is additionally gated
+// by l1_map[pixel] >= *tau, read from the stored map so that the selection is exactly a function
+// of the map the threshold was selected on. A separate instantiation: BS = 0 is the kernel as it
+// was (the two LossArgs pointers are never read).
+template <int C1, int C2, int C3, int YF = 0, int BS = 0>
 __global__ __launch_bounds__(THREADS) void loss_head_kernel(LossArgs a, LossTables t) {
   constexpr int CT = C1 + C2 + C3;
   constexpr int WIN_R = LA + 2, WIN_C = LB + 2;
@@ -131,6 +136,8 @@ __global__ __launch_bounds__(THREADS) void loss_head_kernel(LossArgs a, LossTabl
 
   float s1 = 0.f, s2v = 0.f, s2h = 0.f, c1n = 0.f, c2vn = 0.f, c2hn = 0.f;
   const bool strong = n < a.npp;
+  float tau = 0.f;
+  if constexpr (BS) tau = *a.tau;
   const float* soft = nullptr;
   if (!strong) {
     soft = (n < a.npp + a.npb) ? a.bbox_soft + (size_t)(n - a.npp) * a.H * a.W * t.n_pb
@@ -268,6 +275,7 @@ __global__ __launch_bounds__(THREADS) void loss_head_kernel(LossArgs a, LossTabl
           const int lab = a.px_labels[pix];
           l1lab = t.pp2l1[lab];
           w1 = l1lab <= t.l1_wmax ? 1.f : 0.f;
+          if constexpr (BS) w1 = (w1 != 0.f && a.l1_map[pix] >= tau) ? 1.f : 0.f;
           const int v = t.pp2veh[lab], hm = t.pp2hum[lab];
 #pragma unroll
           for (int c = 0; c < C2; ++c) y2[c] = c == v ? 1.f : 0.f;
@@ -693,6 +701,58 @@ __global__ __launch_bounds__(256) void full_predictions_kernel(FullPredArgs a, L
   }
 }
 
+// Per-pixel l1 loss map of the strong images (bootstrapped loss, launch_l1_loss_map): one thread
+// per full-resolution pixel, the 4 low-res source cells read through L2, the l1 channels only.
+// The same expressions as loss_head_kernel (lerp_of, top/bot lerp, max, __expf sum, logf), so the
+// two agree on what a pixel's logits and loss are. Unweighted pixels store +0.0f; the loss is
+// lse - (x_label - max) with lse >= 0 and x_label - max <= 0, clamped to [+0, FLT_MAX] so that a
+// rounding artefact or a non-finite logit cannot break the bit ordering the select relies on.
+template <int C1>
+__global__ __launch_bounds__(256) void l1_loss_map_kernel(LossArgs a, LossTables t,
+                                                          float* __restrict__ map) {
+  const long total = (long)a.npp * a.H * a.W;
+  for (long id = (long)blockIdx.x * blockDim.x + threadIdx.x; id < total;
+       id += (long)gridDim.x * blockDim.x) {
+    const int w = (int)(id % a.W);
+    const int h = (int)((id / a.W) % a.H);
+    const int n = (int)(id / ((long)a.W * a.H));
+    const int lab = a.px_labels[id];
+    const int l1lab = (lab >= 0 && lab < t.n_pp) ? t.pp2l1[lab] : -1;
+    float v = 0.f;
+    if (l1lab >= 0 && l1lab <= t.l1_wmax) {
+      int ylo, yhi, xlo, xhi;
+      float yl, xl;
+      lerp_of(h, a.Hl, a.H, ylo, yhi, yl);
+      lerp_of(w, a.Wl, a.W, xlo, xhi, xl);
+      const float* base = a.logits + (size_t)n * a.Hl * a.Wl * a.ldl;
+      const float* tl = base + ((size_t)ylo * a.Wl + xlo) * a.ldl;
+      const float* tr = base + ((size_t)ylo * a.Wl + xhi) * a.ldl;
+      const float* bl = base + ((size_t)yhi * a.Wl + xlo) * a.ldl;
+      const float* br = base + ((size_t)yhi * a.Wl + xhi) * a.ldl;
+      float x[C1];
+#pragma unroll
+      for (int c = 0; c < C1; ++c) {
+        float top = tl[c] + (tr[c] - tl[c]) * xl;
+        float bot = bl[c] + (br[c] - bl[c]) * xl;
+        x[c] = top + (bot - top) * yl;
+      }
+      float m1 = x[0];
+#pragma unroll
+      for (int c = 1; c < C1; ++c) m1 = fmaxf(m1, x[c]);
+      float s = 0.f;
+#pragma unroll
+      for (int c = 0; c < C1; ++c) s += __expf(x[c] - m1);
+      const float lse1 = logf(s);
+      float xl1 = 0.f;
+#pragma unroll
+      for (int c = 0; c < C1; ++c) if (c == l1lab) xl1 = x[c];
+      const float ce = lse1 - (xl1 - m1);
+      v = ce > 0.f ? fminf(ce, 3.402823466e38f) : 0.f;   // NaN -> +0
+    }
+    map[id] = v;
+  }
+}
+
 __global__ void confusion_global_kernel(const int* __restrict__ lab, const int* __restrict__ dec,
                                         long n, int nc, int* cm) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
@@ -717,12 +777,39 @@ bool loss_head_yf(int W, int Wl) {
 hipError_t launch_loss_head(const LossArgs& a, const LossTables& t, hipStream_t s) {
   dim3 g(loss_head_blocks(a.N, a.Hl, a.Wl));
   const bool yf = loss_head_yf(a.W, a.Wl);
+  if ((a.l1_map != nullptr) != (a.tau != nullptr)) return hipErrorInvalidValue;
+  if (a.l1_map) {   // bootstrapped l1 weights: the gated instantiations
+    if (t.c1 == 14 && t.c2 == 7 && t.c3 == 3 && yf)
+      hipLaunchKernelGGL((loss_head_kernel<14, 7, 3, 1, 1>), g, dim3(THREADS), 0, s, a, t);
+    else if (t.c1 == 14 && t.c2 == 7 && t.c3 == 3)
+      hipLaunchKernelGGL((loss_head_kernel<14, 7, 3, 0, 1>), g, dim3(THREADS), 0, s, a, t);
+    else if (t.c1 == 53 && t.c2 == 12 && t.c3 == 5)
+      hipLaunchKernelGGL((loss_head_kernel<53, 12, 5, 0, 1>), g, dim3(THREADS), 0, s, a, t);
+    else
+      return hipErrorInvalidValue;
+    return hipGetLastError();
+  }
   if (t.c1 == 14 && t.c2 == 7 && t.c3 == 3 && yf)
     hipLaunchKernelGGL((loss_head_kernel<14, 7, 3, 1>), g, dim3(THREADS), 0, s, a, t);
   else if (t.c1 == 14 && t.c2 == 7 && t.c3 == 3)
     hipLaunchKernelGGL((loss_head_kernel<14, 7, 3>), g, dim3(THREADS), 0, s, a, t);
   else if (t.c1 == 53 && t.c2 == 12 && t.c3 == 5)
     hipLaunchKernelGGL((loss_head_kernel<53, 12, 5>), g, dim3(THREADS), 0, s, a, t);
+  else
+    return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+hipError_t launch_l1_loss_map(const LossArgs& a, const LossTables& t, float* map, hipStream_t s) {
+  const long total = (long)a.npp * a.H * a.W;
+  if (total <= 0) return hipSuccess;
+  if (!map || !a.px_labels) return hipErrorInvalidValue;
+  long g = (total + 255) / 256;
+  if (g > 16384) g = 16384;
+  if (t.c1 == 14)
+    hipLaunchKernelGGL((l1_loss_map_kernel<14>), dim3((int)g), dim3(256), 0, s, a, t, map);
+  else if (t.c1 == 53)
+    hipLaunchKernelGGL((l1_loss_map_kernel<53>), dim3((int)g), dim3(256), 0, s, a, t, map);
   else
     return hipErrorInvalidValue;
   return hipGetLastError();

@@ -14,6 +14,7 @@
 
 #include "../../include/seg_hip.h"
 #include "bn.h"
+#include "bootstrap.h"
 #include "lbf.h"
 #include "input.h"
 #include "augment.h"
@@ -214,6 +215,14 @@ struct seg_ctx {
   bool premask = true;             // seg_set_premask: pre-masked identity-unit gradients (unit_backward)
   int64_t premask_launches = 0;    // conv1 data gradients stored pre-masked (seg_counter)
   int64_t loss_yf_launches = 0;    // loss heads run by the y-first kernel (seg_counter)
+  // bootstrapped l1 loss (seg_set_bootstrap): percentage (<= 0 off), K of this context's
+  // npp * H * W map entries, the per-pixel loss map, the select's slab and device state
+  int bs_pct = 0;
+  int64_t bs_k = 0;
+  float* bs_map = nullptr;         // [npp][H][W]
+  unsigned* bs_slab = nullptr;
+  BootstrapState* bs_state = nullptr;
+  int64_t bootstrap_launches = 0;  // seg_loss calls that ran map + select + gated head (seg_counter)
   bool prestem_rec = false;
   bool stem_pending = false;
   float* dzscale = nullptr;       // [ldl]
@@ -2031,6 +2040,14 @@ int seg_loss(seg_ctx* c, const int32_t* px, const float* bbox, const float* tag,
   a.px_labels = px; a.bbox_soft = bbox; a.tag_soft = tag;
   a.grad_un = c->grad_un; a.part = c->loss_part; a.decisions = decisions;
   hipStream_t s = (hipStream_t)stream;
+  if (c->bs_pct > 0 && g.nb_pp > 0) {   // bootstrapped l1: map -> K-th largest -> gated head
+    HIPCALL(c, launch_l1_loss_map(a, c->tables, c->bs_map, s));
+    HIPCALL(c, launch_bootstrap_select(c->bs_map, (long long)g.nb_pp * g.height * g.width, c->bs_k,
+                                       c->bs_slab, c->bs_state, s));
+    a.l1_map = c->bs_map;
+    a.tau = &c->bs_state->tau;
+    ++c->bootstrap_launches;
+  }
   HIPCALL(c, launch_loss_head(a, c->tables, s));
   if (c->tables.c1 == 14 && loss_head_yf(a.W, a.Wl)) ++c->loss_yf_launches;
   HIPCALL(c, launch_loss_finalize(c->loss_part, c->loss_blocks, c->tables, c->ldl, c->loss_scale,
@@ -2209,12 +2226,56 @@ int seg_set_lbf(seg_ctx* c, int on) {
   return 0;
 }
 
+int seg_set_bootstrap(seg_ctx* c, int percentage) {
+  if (!c) return set_err(nullptr, -EINVAL, "null ctx");
+  if (percentage > 100)
+    return set_err(&c->err, -EINVAL, "bootstrapping_percentage %d: must be at most 100 (<= 0 disables "
+                   "bootstrapping)", percentage);
+  if (percentage <= 0 || c->cfg.nb_pp <= 0) {   // off; without strong images there is no l1 loss
+    c->bs_pct = 0;
+    return 0;
+  }
+  const int64_t M = (int64_t)c->cfg.nb_pp * c->cfg.height * c->cfg.width;
+  if (M > 2147483647ll) return set_err(&c->err, -EINVAL, "bootstrapping: %lld map entries", (long long)M);
+  if (!c->bs_map) {   // first enable (outside any step); freed with the context's allocations
+    if (int r = dalloc(c, &c->bs_map, (size_t)M)) return r;
+    if (int r = dalloc(c, &c->bs_slab, BOOTSTRAP_SLAB_BYTES / sizeof(unsigned))) return r;
+    if (int r = dalloc(c, &c->bs_state, 1)) return r;
+  }
+  c->bs_pct = percentage;
+  c->bs_k = std::max<int64_t>(1, (int64_t)percentage * M / 100);
+  return 0;
+}
+
+int seg_op_bootstrap_threshold(const float* map, int64_t n, int64_t k, float* tau_out,
+                               int64_t* n_ge_out, void* stream) {
+  if (!map || !tau_out || !n_ge_out) return set_err(nullptr, -EINVAL, "seg_op_bootstrap_threshold: null argument");
+  if (n < 1 || n > 2147483647ll || k < 1 || k > n)
+    return set_err(nullptr, -EINVAL, "seg_op_bootstrap_threshold: need 1 <= k <= n <= 2^31 - 1 (k %lld, n %lld)",
+                   (long long)k, (long long)n);
+  hipStream_t s = (hipStream_t)stream;
+  void* ws = nullptr;
+  hipError_t e = hipMalloc(&ws, BOOTSTRAP_SLAB_BYTES + sizeof(BootstrapState));
+  if (e != hipSuccess) return hip_fail(nullptr, e, "seg_op_bootstrap_threshold");
+  BootstrapState* st = (BootstrapState*)((char*)ws + BOOTSTRAP_SLAB_BYTES);
+  BootstrapState host{};
+  e = launch_bootstrap_select(map, n, k, (unsigned*)ws, st, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  (void)hipFree(ws);
+  if (e != hipSuccess) return hip_fail(nullptr, e, "seg_op_bootstrap_threshold");
+  *tau_out = host.tau;
+  *n_ge_out = host.n_ge;
+  return 0;
+}
+
 int seg_counter(seg_ctx* c, const char* name, int64_t* value) {
   if (!c || !name || !value) return set_err(c ? &c->err : nullptr, -EINVAL, "null argument");
   const std::string n(name);
   if (n == "premask_launches") *value = c->premask_launches;
   else if (n == "lbf_layers") *value = c->lbf_launches;
   else if (n == "loss_yf_launches") *value = c->loss_yf_launches;
+  else if (n == "bootstrap_launches") *value = c->bootstrap_launches;
   else return set_err(&c->err, -ENOENT, "unknown counter '%s'", name);
   return 0;
 }
@@ -2464,6 +2525,13 @@ int seg_debug_tensor(seg_ctx* c, const char* name, void** ptr, int* dims, int* l
   else if (n == "head_in") { a = c->logits; a.p = (void*)c->head_in; dt = SEG_DTYPE_F32; }
   else if (n == "grad_un") { a = c->logits; a.p = c->grad_un; dt = SEG_DTYPE_F32; }
   else if (n == "dzscale") { a.p = c->dzscale; a.N = a.H = a.W = 1; a.C = a.ld = c->ldl; dt = SEG_DTYPE_F32; }
+  else if (n == "l1_loss_map" || n == "bootstrap_tau") {
+    if (!c->bs_map) return set_err(&c->err, -EINVAL, "%s: bootstrapping was never enabled (seg_set_bootstrap)", name);
+    dt = SEG_DTYPE_F32;
+    a.C = a.ld = 1;
+    if (n == "l1_loss_map") { a.p = c->bs_map; a.N = c->cfg.nb_pp; a.H = c->cfg.height; a.W = c->cfg.width; }
+    else { a.p = &c->bs_state->tau; a.N = a.H = a.W = 1; }
+  }
   else if (n == "feat") a = c->feat;
   else if (n == "dfeat") a = c->dfeat;
   else if (n == "z0") {   // stem BN + ReLU output (the max-pool input)

@@ -18,7 +18,7 @@ from __future__ import annotations
 
 from collections import namedtuple
 
-from estimator.define_losses_hierarchical import define_losses
+from estimator.define_losses_hierarchical import configure_bootstrap, define_losses
 from estimator.define_optimizer import DynamicLossScaler, define_optimizer
 from estimator.mode_keys import ModeKeys
 
@@ -112,6 +112,9 @@ def define_estimator(mode, features, labels, model_fn, config, params):
     # backward); bf16 / fp32 need none
     if getattr(ctx, 'dtype', None) == 'fp16' and getattr(ctx, '_scaler', None) is None:
         ctx._scaler = DynamicLossScaler(ctx)
+    # --bootstrapping_percentage: the l1 loss over the hardest p % of the strong pixels
+    # (seg_set_bootstrap); read once here, before the loss head of this step runs
+    configure_bootstrap(ctx, params)
     losses = define_losses(mode, predictions, labels, config, params)
     optimizer = define_optimizer(global_step, params)
     if getattr(ctx, 'nesterov', False) != optimizer.use_nesterov:

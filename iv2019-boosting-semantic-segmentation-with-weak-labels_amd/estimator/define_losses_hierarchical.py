@@ -40,6 +40,20 @@ class Losses(dict):
         return tuple(int(v) for v in self._losses[4:7].tolist())
 
 
+def configure_bootstrap(ctx, params):
+    """--bootstrapping_percentage -> ctx.set_bootstrap, once per change of the value (params None
+    or without the field leaves the context as it is). > 100 is an error here as in the library."""
+    p = getattr(params, 'bootstrapping_percentage', None)
+    if p is None:
+        return
+    p = int(p)
+    if p > 100:
+        raise ValueError(f'bootstrapping_percentage {p}: must be at most 100 (-1 disables bootstrapping).')
+    p = p if p > 0 else -1
+    if getattr(ctx, 'bootstrap', -1) != p:
+        ctx.set_bootstrap(p)
+
+
 def define_losses(mode, predictions, labels, config, params):  # pylint: disable=unused-argument
     if mode == ModeKeys.EVAL:
         import torch
@@ -48,6 +62,7 @@ def define_losses(mode, predictions, labels, config, params):  # pylint: disable
     if mode != ModeKeys.TRAIN:
         raise NotImplementedError(f"mode {mode} is invalid or not yet implemented.")
     ctx = predictions['_context']
+    configure_bootstrap(ctx, params)   # a no-op when define_estimator has configured the context
     px = labels.get('prolabels_per_pixel')
     bb = labels.get('prolabels_per_bbox')
     tg = labels.get('prolabels_per_image')

@@ -32,7 +32,7 @@ EXPORTED_SYMBOLS = [
     "seg_counter",
     "seg_crc32c", "seg_prepare_images", "seg_prepare_labels", "seg_prepare_images_crop",
     "seg_bbox_labels_flip", "seg_augment_workspace", "seg_augment_images", "seg_augment_labels", "seg_augment_profile",
-    "seg_augment_profile_blur",
+    "seg_augment_profile_blur", "seg_set_bootstrap", "seg_op_bootstrap_threshold",
 ]
 
 # int (*seg_allreduce_fn)(void* user, float* buf, int64_t n, void* stream)
@@ -138,6 +138,8 @@ def _load():
         "seg_set_premask": (ip, [vp, ip]),
         "seg_set_lbf": (ip, [vp, ip]),
         "seg_counter": (ip, [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64)]),
+        "seg_set_bootstrap": (ip, [vp, ip]),
+        "seg_op_bootstrap_threshold": (ip, [vp, i64, i64, ctypes.POINTER(f), ctypes.POINTER(i64), vp]),
     }
     override = "SEG_HIP_LIB" in os.environ   # A/B builds of older commits may lack new entries
     for name, (res, args) in sig.items():
@@ -400,6 +402,12 @@ class SegContext:
         off = the separate BN-backward apply pass, the fold's reference path in tests)."""
         check(LIB.seg_set_lbf(self.h, 1 if on else 0), self.h)
 
+    def set_bootstrap(self, percentage: int):
+        """seg_set_bootstrap: bootstrapped l1 loss over the hardest `percentage` % of the strong
+        images' pixels (--bootstrapping_percentage); <= 0 turns it off, > 100 is an error."""
+        check(LIB.seg_set_bootstrap(self.h, int(percentage)), self.h)
+        self.bootstrap = int(percentage) if percentage > 0 else -1
+
     def counter(self, name: str) -> int:
         """seg_counter: a runtime counter since creation (e.g. "premask_launches")."""
         v = ctypes.c_int64()
@@ -498,6 +506,16 @@ class SegContext:
             self.close()
         except Exception:
             pass
+
+
+def bootstrap_threshold(values, k: int, stream=None):
+    """seg_op_bootstrap_threshold on a contiguous device float32 tensor of finite values >= +0:
+    (rc, tau, n_ge) with tau the k-th largest entry and n_ge the count of entries >= tau; rc is
+    the library's return code (-EINVAL for k outside 1..n), not raised."""
+    tau, n_ge = ctypes.c_float(), ctypes.c_int64()
+    rc = LIB.seg_op_bootstrap_threshold(_ptr(values), values.numel(), int(k), ctypes.byref(tau),
+                                        ctypes.byref(n_ge), _stream(stream))
+    return rc, tau.value, n_ge.value
 
 
 def _wrap_u16(ptr: int, shape: Tuple[int, ...], device, half=False):

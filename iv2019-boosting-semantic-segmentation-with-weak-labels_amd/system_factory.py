@@ -352,6 +352,9 @@ def _validate_settings(settings):
         if not (bool(settings.learning_rate_decay) != bool(settings.learning_rate_values)):
             raise AttributeError('If `learning_rate_schedule` is `piecewise_constant` exactly one '
                                  'of `learning_rate_decay` or `learning_rate_values` must be given.')
+    if int(getattr(settings, 'bootstrapping_percentage', -1) or -1) > 100:
+        raise ValueError(f'bootstrapping_percentage {settings.bootstrapping_percentage}: must be at '
+                         'most 100 (-1 disables bootstrapping).')
     lids2cids_unique = set(settings.training_problem_def['lids2cids'])
     cid_max = max(lids2cids_unique)
     lids2cids_unique.discard(-1)
