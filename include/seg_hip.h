@@ -412,6 +412,21 @@ int seg_op_conv_dgrad_fused(int dtype, const void* dy, int N, int H, int W, int 
                             const void* r1, int ldr1, const void* r2, int ldr2, const void* dy2,
                             int Co2, int lddy2, const void* wt2, const uint8_t* omask,
                             void* stream);
+/* read-only: which kernel a conv request runs on (csrc/conv_select.h), written into buf as one
+ * line of key=value words, e.g. "kernel=pp tile=256x256 st=0 persist=1 ... stat_rows=128
+ * omask=0 wgs=4096 lds=131072", or "kernel=invalid reason=..." (the reason runs to the end of
+ * the line). No GPU is touched. f = the nf scalar fields of the argument struct in declaration
+ * order (csrc/conv_args.h):
+ *   conv (nf 24): N H W C ldx ldw Ho Wo Co ldy ldr ldr2 KH KW sf st pad_h pad_w dil tap8 ldx2 C2
+ *                 ldw2 ldm; flags: 1 residual, 2 second residual, 4 statistics, 8 mask,
+ *                 16 second GEMM
+ *   wgrad (nf 18): lddy N H W C ldx Ho Wo Co KH KW sf pad_h pad_w dil splits lddy2 Co1;
+ *                 flags: 1 second dy source; force_bm / force_bn: 0, or the forced tile of
+ *                 seg_op_conv_wgrad_cfg
+ * Returns 0, -EINVAL for a bad argument, -ENOSPC when len is too small. */
+int seg_op_conv_plan(int dtype, int out_f32, const int* f, int nf, int flags, char* buf, int len);
+int seg_op_conv_wgrad_plan(int dtype, const int* f, int nf, int flags, int force_bm, int force_bn,
+                           char* buf, int len);
 /* the threshold select of seg_set_bootstrap on any device array of n finite floats >= +0 (a set
  * sign bit, -0.0f included, is outside the contract): *tau_out = the k-th largest entry,
  * *n_ge_out = the count of entries >= tau (both host pointers; the call synchronises `stream`

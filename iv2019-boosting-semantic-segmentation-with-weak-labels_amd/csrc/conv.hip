@@ -15,6 +15,7 @@
 // (bf16) so each lane receives 8 consecutive pixels of one column. Split-K over pixels
 // into fp32 slabs, reduced in a fixed order by splitk_reduce (bitwise reproducible).
 #include "conv.h"
+#include "conv_launch.h"
 
 namespace {
 
@@ -601,12 +602,11 @@ hipError_t nt_launch(const ConvArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// the conv_nt_kernel instantiation a plan names
 template <typename T, typename TO>
-hipError_t nt_dispatch(const ConvArgs& a, hipStream_t s) {
-  const bool generic = (a.C % MmaT<T>::BK) != 0 || (a.ldx % (16 / (int)sizeof(T))) != 0 ||
-                       (a.ldw % (16 / (int)sizeof(T))) != 0;
-  if (generic) return nt_launch<T, TO, 128, 64, true>(a, s);
-  if (a.Co <= 64) return nt_launch<T, TO, 128, 64, false>(a, s);
+hipError_t nt_mfma(const ConvNtPlan& p, const ConvArgs& a, hipStream_t s) {
+  if (p.generic) return nt_launch<T, TO, 128, 64, true>(a, s);
+  if (p.bn == 64) return nt_launch<T, TO, 128, 64, false>(a, s);
   return nt_launch<T, TO, 128, 128, false>(a, s);
 }
 
@@ -618,27 +618,20 @@ hipError_t wg_launch(const WgradArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// the conv_wgrad_kernel instantiation a plan names
 template <typename T>
-hipError_t wg_dispatch(const WgradArgs& a, hipStream_t s) {
-  const int epc = 16 / (int)sizeof(T);
-  const bool generic = (a.C % epc) != 0 || (a.ldx % epc) != 0;
-  if (a.Co % epc != 0 || a.lddy % epc != 0) return hipErrorInvalidValue;
-  const int BM = a.Co <= 64 ? 64 : 128;
-  if (generic) {
-    if (BM == 64) return wg_launch<T, 64, 64, true>(a, s);
+hipError_t wg_mfma(const ConvWgradPlan& p, const WgradArgs& a, hipStream_t s) {
+  if (p.generic) {
+    if (p.bm == 64) return wg_launch<T, 64, 64, true>(a, s);
     return wg_launch<T, 128, 64, true>(a, s);
   }
-  if (BM == 64) return wg_launch<T, 64, 128, false>(a, s);
+  if (p.bm == 64) return wg_launch<T, 64, 128, false>(a, s);
   return wg_launch<T, 128, 128, false>(a, s);
 }
 
 }  // namespace
 
 int conv_nt_mtiles(long M) { return ceil_div(M, 128); }
-
-int conv_nt_stat_rows(int dtype, int out_f32, const ConvArgs& a) {
-  return (seg_half(dtype) && !out_f32 && conv_nt_v2_ok(a)) ? conv_nt_v2_rows(a) : 128;
-}
 
 namespace {
 template <typename E>
@@ -773,32 +766,38 @@ hipError_t launch_splitk_reduce_s2d(const float* part, int splits, long split_st
   return hipGetLastError();
 }
 
-bool conv_nt_uses_v2(int dtype, int out_f32, const ConvArgs& a) {
-  return seg_half(dtype) && !out_f32 && conv_nt_v2_ok(a);
-}
+static_assert(CONV_SEL_F32 == SEG_F32 && CONV_SEL_BF16 == SEG_BF16 && CONV_SEL_F16 == SEG_F16,
+              "conv_select.h's element types are SegDType's");
 
 hipError_t launch_conv_nt(int dtype, int out_f32, const ConvArgs& a, hipStream_t s) {
-  if (a.omask && (out_f32 || !conv_nt_omask_ok(dtype, a))) return hipErrorInvalidValue;
-  if (conv_nt_uses_v2(dtype, out_f32, a)) return launch_conv_nt_v2(dtype, a, s);
-  if (conv_skinny_ok(dtype, out_f32, a)) return launch_conv_skinny(dtype, a, s);
-  if (dtype == SEG_BF16) {
-    if (out_f32) return nt_dispatch<bf16_t, float>(a, s);
-    return nt_dispatch<bf16_t, bf16_t>(a, s);
+  const ConvNtPlan p = conv_nt_plan(dtype, out_f32, a);
+  switch (p.kernel) {
+    case NT_V2: case NT_V2_DUAL: case NT_PATCH: case NT_PATCH_S2D:
+      return launch_conv_nt_tile(dtype, p, a, s);
+    case NT_PP: return launch_conv_nt_pp(dtype, p, a, s);
+    case NT_SKINNY_N: case NT_SKINNY_K: return launch_conv_skinny(dtype, p, a, s);
+    case NT_MFMA:
+      if (dtype == SEG_BF16)
+        return p.out_f32 ? nt_mfma<bf16_t, float>(p, a, s) : nt_mfma<bf16_t, bf16_t>(p, a, s);
+      if (dtype == SEG_F16)
+        return p.out_f32 ? nt_mfma<f16_t, float>(p, a, s) : nt_mfma<f16_t, f16_t>(p, a, s);
+      return nt_mfma<float, float>(p, a, s);
   }
-  if (dtype == SEG_F16) {
-    if (out_f32) return nt_dispatch<f16_t, float>(a, s);
-    return nt_dispatch<f16_t, f16_t>(a, s);
-  }
-  return nt_dispatch<float, float>(a, s);
+  return hipErrorInvalidValue;
 }
 
-hipError_t launch_conv_wgrad(int dtype, const WgradArgs& a, hipStream_t s) {
-  if (a.dy2 && !(seg_half(dtype) && a.KH == 1 && a.KW == 1 && conv_wgrad_v2_ok(a))) return hipErrorInvalidValue;
-  if (seg_half(dtype) && conv_wgrad_patch_ok(a)) return launch_conv_wgrad_patch(dtype, a, s);
-  if (seg_half(dtype) && conv_wgrad_v2_ok(a)) return launch_conv_wgrad_v2(dtype, a, s);
-  if (dtype == SEG_BF16) return wg_dispatch<bf16_t>(a, s);
-  if (dtype == SEG_F16) return wg_dispatch<f16_t>(a, s);
-  return wg_dispatch<float>(a, s);
+hipError_t launch_conv_wgrad(int dtype, const WgradArgs& a, hipStream_t s, int force_bm, int force_bn) {
+  const ConvWgradPlan p = conv_wgrad_plan(dtype, a, force_bm, force_bn);
+  switch (p.kernel) {
+    case WG_PATCH: return launch_conv_wgrad_patch(dtype, p, a, s);
+    case WG_V2: return launch_conv_wgrad_v2(dtype, p, a, s);
+    case WG_PP: return launch_conv_wgrad_pp(dtype, p, a, s);
+    case WG_MFMA:
+      if (dtype == SEG_BF16) return wg_mfma<bf16_t>(p, a, s);
+      if (dtype == SEG_F16) return wg_mfma<f16_t>(p, a, s);
+      return wg_mfma<float>(p, a, s);
+  }
+  return hipErrorInvalidValue;
 }
 
 hipError_t launch_splitk_reduce(const float* part, int splits, long split_stride, long n,

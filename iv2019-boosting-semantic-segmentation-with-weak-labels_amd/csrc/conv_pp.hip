@@ -29,6 +29,7 @@
 //    gradients with one residual (dense 1 x 1 rows) take the residual tile by LDS-DMA and add it
 //    in place (RQP, PERSIST = 3); two residuals or other shapes run one tile per workgroup.
 #include "conv.h"
+#include "conv_launch.h"
 #include <cstdlib>
 
 #ifdef PP_DBG_TIMING
@@ -535,7 +536,7 @@ __device__ __forceinline__ void conv_nt_pp_body(const ConvArgs& a) {
     const int nbase = n0 + wn * 32 + lq * 4;
     // per channel (sum, M2) over the wave row's rows: 8 values in the lane, then a butterfly
     // over the 16 lanes (lr) holding the same channels; one partial per 128 rows
-    // (conv_nt_stat_rows); the ragged last tile merges with per-lane counts. Run per column
+    // (ConvNtPlan::stat_rows); the ragged last tile merges with per-lane counts. Run per column
     // half between that half's staging writes and the barrier, so the VALU work overlaps the
     // LDS traffic and the other waves' arrival
     const bool full = nvalid == 128;
@@ -861,6 +862,7 @@ template <typename E, int ST, int PERSIST>
 hipError_t pp_launch(const ConvArgs& a, hipStream_t s) {
   // two K-tile buffers (the epilogue stages through buffer 1; RQP: the residual tile)
   constexpr int LDS = PP_LDS;
+  static_assert(LDS == CONV_NT_PP_LDS, "the plan's LDS (conv_select.h)");
   auto kern = conv_nt_pp_kernel<E, ST, PERSIST>;
   static bool attr = false;
   if (!attr) {
@@ -874,52 +876,34 @@ hipError_t pp_launch(const ConvArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// the instantiation a plan names: ST (0 dense 1 x 1 rows, 4 dense rows + the second GEMM, 1 / 2
+// the gathered strides) and PERSIST (3: dense rows with one residual, its tile by LDS-DMA)
 template <typename E, int ST>
-hipError_t pp_launch_st(const ConvArgs& a, hipStream_t s) {
-  if constexpr (ST == 0) {   // dense 1 x 1 rows, one residual: the residual tile by LDS-DMA
-    if (a.r && !a.r2 && (long)a.N * a.Ho * a.Wo * a.ldr * 2 < (1L << 31))
-      return pp_launch<E, 0, 3>(a, s);
+hipError_t pp_launch_st(const ConvNtPlan& p, const ConvArgs& a, hipStream_t s) {
+  if constexpr (ST == 0) {
+    if (p.persist == 3) return pp_launch<E, 0, 3>(a, s);
   }
-  if (a.r || a.r2 || a.omask) return pp_launch<E, ST, 0>(a, s);
-  return pp_launch<E, ST, 1>(a, s);
+  if (p.persist == 0) return pp_launch<E, ST, 0>(a, s);
+  if (p.persist == 1) return pp_launch<E, ST, 1>(a, s);
+  return hipErrorInvalidValue;
+}
+
+template <typename E>
+hipError_t nt_pp_e(const ConvNtPlan& p, const ConvArgs& a, hipStream_t s) {
+  switch (p.st) {
+    case 0: return pp_launch_st<E, 0>(p, a, s);
+    case 1: return pp_launch_st<E, 1>(p, a, s);
+    case 2: return pp_launch_st<E, 2>(p, a, s);
+    case 4: return pp_launch_st<E, 4>(p, a, s);
+  }
+  return hipErrorInvalidValue;
 }
 
 }  // namespace
 
-// ping-pong config: the v2 fast-path preconditions (conv_nt_v2_ok, no tap8), Co > 128 and an
-// operands of < 2^31 bytes (32-bit buffer offsets), kernels up to 4 x 4 (tap validity bits)
-bool conv_nt_pp_ok(const ConvArgs& a) {
-  // 16-byte epilogue stores: channel counts and row strides multiples of 8
-  return !a.tap8 && a.Co > 128 && a.Co % 8 == 0 && a.ldy % 8 == 0 &&
-         a.KH <= 4 && a.KW <= 4 && conv_nt_v2_ok(a) &&
-         (long)a.N * a.H * a.W * a.ldx * 2 < (1L << 31) && (long)a.Co * a.ldw * 2 < (1L << 31) &&
-         (long)a.N * a.Ho * a.Wo < (1L << 31) &&   // 32-bit pixel indices
-         (!a.x2 || (a.KH == 1 && a.KW == 1 && a.st == 1 && a.sf == 1 && a.pad_h == 0 && a.pad_w == 0 &&
-                    a.H == a.Ho && a.W == a.Wo && a.C % 64 == 0 && a.C2 % 64 == 0 && a.ldx2 % 8 == 0 &&
-                    a.ldw2 % 8 == 0 && (long)a.N * a.H * a.W * a.ldx2 * 2 < (1L << 31) &&
-                    (long)a.Co * a.ldw2 * 2 < (1L << 31) && !a.r && !a.r2));
-}
-
-bool conv_nt_omask_ok(int dtype, const ConvArgs& a) {
-  return seg_half(dtype) && !a.tap8 && a.st == 1 && a.KH == 1 && a.KW == 1 && a.sf == 1 &&
-         a.pad_h == 0 && a.pad_w == 0 && a.H == a.Ho && a.W == a.Wo && a.Co > 128 &&
-         conv_nt_pp_ok(a) && a.ldm >= a.Co / 8;
-}
-
-template <typename E>
-hipError_t nt_pp_e(const ConvArgs& a, hipStream_t s) {
-  if (a.st == 1 && a.KH == 1 && a.KW == 1 && a.sf == 1 && a.pad_h == 0 && a.pad_w == 0 &&
-      a.H == a.Ho && a.W == a.Wo)
-    return a.x2 ? pp_launch_st<E, 4>(a, s)    // dense 1x1 rows + the second GEMM
-                : pp_launch_st<E, 0>(a, s);   // dense 1x1 rows
-  if (a.st == 1) return pp_launch_st<E, 1>(a, s);
-  if (a.st == 2) return pp_launch_st<E, 2>(a, s);
-  return hipErrorInvalidValue;
-}
-
-hipError_t launch_conv_nt_pp(int dtype, const ConvArgs& a, hipStream_t s) {
-  if (dtype == SEG_F16) return nt_pp_e<f16_t>(a, s);
-  return nt_pp_e<bf16_t>(a, s);
+hipError_t launch_conv_nt_pp(int dtype, const ConvNtPlan& p, const ConvArgs& a, hipStream_t s) {
+  if (dtype == SEG_F16) return nt_pp_e<f16_t>(p, a, s);
+  return nt_pp_e<bf16_t>(p, a, s);
 }
 
 // ======================================================================================
@@ -1302,16 +1286,9 @@ __global__ __launch_bounds__(PP_THREADS, 1) void conv_wgrad_pp_kernel(WgradArgs 
 
 }  // namespace
 
-// 256 x 256 wgrad tiles with operands < 2^31 bytes (32-bit buffer offsets)
-bool conv_wgrad_pp_ok(const WgradArgs& a) {
-  const long P = (long)a.N * a.Ho * a.Wo;
-  return (a.C % 8) == 0 && (a.ldx % 8) == 0 && (a.Co % 8) == 0 && (a.lddy % 8) == 0 &&
-         P * a.lddy * 2 < (1L << 31) && (long)a.N * a.H * a.W * a.ldx * 2 < (1L << 31) &&
-         (!a.dy2 || (a.Co1 % 256 == 0 && a.Co1 < a.Co && a.lddy2 % 8 == 0 && P * a.lddy2 * 2 < (1L << 31)));
-}
-
-hipError_t launch_conv_wgrad_pp(int dtype, const WgradArgs& a, hipStream_t s) {
+hipError_t launch_conv_wgrad_pp(int dtype, const ConvWgradPlan& p, const WgradArgs& a, hipStream_t s) {
   const int Ncol = a.KH * a.KW * a.C;
+  static_assert(WPP_LDS == CONV_WGRAD_PP_LDS, "the plan's LDS (conv_select.h)");
   const int nwg = ceil_div(a.Co, 256) * ceil_div(Ncol, 256) * a.splits;
   auto launch = [&](auto kern) -> hipError_t {
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, WPP_LDS);
@@ -1319,16 +1296,14 @@ hipError_t launch_conv_wgrad_pp(int dtype, const WgradArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(kern, dim3(nwg), dim3(PP_THREADS), WPP_LDS, s, a);
     return hipGetLastError();
   };
-  // strip order where the rows split into whole 64-pixel K-tiles and the pixel rows repeat
-  // across taps (KH > 1); 1x1 layers read every x row once, raster order is as good there
-  const bool strip = (a.Wo % 64) == 0 && a.KH > 1;
+  // p.fast: 2 strip order, 1 Wo >= 64, 0 any width (conv_select.cpp)
   if (dtype == SEG_F16) {
-    if (strip) return launch(conv_wgrad_pp_kernel<f16_t, 2>);
-    if (a.Wo >= 64) return launch(conv_wgrad_pp_kernel<f16_t, 1>);
+    if (p.fast == 2) return launch(conv_wgrad_pp_kernel<f16_t, 2>);
+    if (p.fast == 1) return launch(conv_wgrad_pp_kernel<f16_t, 1>);
     return launch(conv_wgrad_pp_kernel<f16_t, 0>);
   }
-  if (strip) return launch(conv_wgrad_pp_kernel<bf16_t, 2>);
-  if (a.Wo >= 64) return launch(conv_wgrad_pp_kernel<bf16_t, 1>);
+  if (p.fast == 2) return launch(conv_wgrad_pp_kernel<bf16_t, 2>);
+  if (p.fast == 1) return launch(conv_wgrad_pp_kernel<bf16_t, 1>);
   return launch(conv_wgrad_pp_kernel<bf16_t, 0>);
 }
 

@@ -14,6 +14,7 @@
 //    store per 8 outputs, and the per-column BN partial statistics (sum, M2 about the tile
 //    mean) for the fused batch-norm.
 #include "conv.h"
+#include "conv_launch.h"
 #include <algorithm>
 #include <cstdlib>
 
@@ -124,7 +125,7 @@ __global__ __launch_bounds__(V2_THREADS, BM_ == 256 ? 1 : 2) void conv_nt_v2_ker
     a_row[i] = row;
     const long m = m0 + row;
     const bool ok = m < M;
-    // 32-bit decode (M < 2^31: conv_nt_v2_ok); the 64-bit div/rem it replaces was a library
+    // 32-bit decode (M < 2^31: conv_select.cpp); the 64-bit div/rem it replaces was a library
     // call per row and per tile
     const unsigned mm = ok ? (unsigned)m : 0u;
     const unsigned t = mm / (unsigned)a.Wo;
@@ -325,7 +326,7 @@ __global__ __launch_bounds__(V2_THREADS, BM_ == 256 ? 1 : 2) void conv_nt_v2_ker
           t.x += u.x;
           nt += (float)WM;
         }
-        if (n0 + c < a.Co)   // one (sum, M2) per BM-row tile (conv_nt_stat_rows)
+        if (n0 + c < a.Co)   // one (sum, M2) per BM-row tile (ConvNtPlan::stat_rows)
           *(float2*)(a.stats + 2 * ((size_t)mt * a.Co + n0 + c)) = t;
       }
     }
@@ -385,7 +386,7 @@ __global__ __launch_bounds__(V2_THREADS, BM_ == 256 ? 1 : 2) void conv_nt_v2_ker
         float t = 0.f;
 #pragma unroll
         for (int w = 0; w < WMW; ++w) t += red[w * BN + c];
-        if (n0 + c < a.Co)   // one (sum, M2) per BM-row tile (conv_nt_stat_rows)
+        if (n0 + c < a.Co)   // one (sum, M2) per BM-row tile (ConvNtPlan::stat_rows)
           *(float2*)(a.stats + 2 * ((size_t)mt * a.Co + n0 + c)) = make_float2(tot[j], t);
       }
     }
@@ -450,6 +451,7 @@ hipError_t v2_launch(const ConvArgs& a, hipStream_t s) {
   constexpr int EPI = BM * (64 + 4) * 4;
   constexpr int LDS = STAGES * STAGE_BYTES > EPI ? STAGES * STAGE_BYTES : EPI;
   static_assert(LDS <= 160 * 1024, "LDS budget");
+  static_assert(LDS == conv_nt_v2_lds(BM, BN), "the plan's LDS (conv_select.h)");
   auto kern = conv_nt_v2_kernel<E, BN, WMW, WNW, STAGES, ST, T8, MF, BM, DU>;
   static bool attr = false;
   if (!attr) {
@@ -823,6 +825,7 @@ template <typename E, int BN, int WMW, int WNW, int NPB, int NST, int OCC>
 hipError_t patch_launch(const ConvArgs& a, hipStream_t s) {
   constexpr int LDS = NPB * PP_BYTES + NST * BN * 128;
   static_assert(LDS * OCC <= 160 * 1024 && LDS >= 256 * (64 + 4) * 4, "LDS budget / epilogue staging");
+  static_assert(LDS == CONV_NT_PATCH_LDS, "the plan's LDS (conv_select.h)");
   auto kern = conv_nt_patch_kernel<E, BN, WMW, WNW, NPB, NST, OCC>;
   static bool attr = false;
   if (!attr) {
@@ -835,18 +838,11 @@ hipError_t patch_launch(const ConvArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-// the stem's patch kernel: the s2d tap mode with 64 output channels on whole 8 x 32 tiles
-bool conv_nt_patch_s2d_ok(const ConvArgs& a) {
-  return a.tap8 == 2 && a.C == 16 && a.ldx == 16 && a.Co == 64 && a.KH == 4 && a.KW == 4 &&
-         a.sf == 1 && a.pad_h == 0 && a.pad_w == 0 && a.dil == 1 && a.ldw >= 256 && a.ldw % 8 == 0 &&
-         a.H == a.Ho + 3 && a.W == a.Wo + 3 && a.Ho % PT_H == 0 && a.Wo % PT_W == 0 && a.ldy % 8 == 0 &&
-         !a.r && !a.r2;
-}
-
 template <typename E>
 hipError_t patch_s2d_launch(const ConvArgs& a, hipStream_t s) {
   constexpr int LDS = 256 * (64 + 4) * 4;   // the epilogue staging (> 16 KB patch + 32 KB weights)
   static_assert(PS_PIX * 32 + 4 * 8192 <= LDS, "LDS");
+  static_assert(LDS == CONV_NT_PATCH_S2D_LDS, "the plan's LDS (conv_select.h)");
   auto kern = conv_nt_patch_s2d_kernel<E>;
   static bool attr = false;
   if (!attr) {
@@ -858,92 +854,44 @@ hipError_t patch_s2d_launch(const ConvArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-// the patch kernel's shapes (see above; measured against the v2 gather in
-// profiles/r02_ab_v19_patch_stem.txt)
-bool conv_nt_patch_ok(const ConvArgs& a) {
-  return !a.tap8 && a.st == 1 && a.sf == 1 && a.dil == 1 && a.KH == 3 && a.KW == 3 &&
-         (a.C == 64 || a.C == 128) && (a.Co == 64 || a.Co == 128) && a.ldw == 9 * a.C &&
-         a.H == a.Ho && a.W == a.Wo && a.Ho % PT_H == 0 && a.Wo % PT_W == 0 &&
-         a.pad_h >= 0 && a.pad_h <= 2 && a.pad_w >= 0 && a.pad_w <= 2 &&
-         a.ldx % 8 == 0 && a.ldy % 8 == 0;
+// the instantiation a plan names (conv_select.cpp picks it; nothing is decided here)
+template <typename E, int ST>
+hipError_t nt_tile_st(const ConvNtPlan& p, const ConvArgs& a, hipStream_t s) {
+  if constexpr (ST == 1) {
+    if (p.kernel == NT_V2_DUAL) {
+      if (p.bn == 128) return v2_launch<E, 128, 4, 2, 3, 1, 0, 16, 256, 1>(a, s);
+      return v2_launch<E, 64, 8, 1, 3, 1, 0, 16, 128, 1>(a, s);
+    }
+    if (p.kernel == NT_PATCH) return patch_launch<E, 64, 8, 1, 1, 3, 2>(a, s);
+  }
+  if (p.kernel != NT_V2) return hipErrorInvalidValue;
+  switch (p.bn) {
+    case 256: return v2_launch<E, 256, 4, 2, 2, ST>(a, s);
+    case 128: return v2_launch<E, 128, 4, 2, 3, ST>(a, s);
+    case 64:
+      if (p.small) return v2_launch<E, 64, 8, 1, 3, ST, 0, 16, 128>(a, s);
+      return v2_launch<E, 64, 8, 1, 3, ST>(a, s);
+  }
+  return hipErrorInvalidValue;
+}
+
+template <typename E>
+hipError_t nt_tile_e(const ConvNtPlan& p, const ConvArgs& a, hipStream_t s) {
+  if (p.tap8) {   // the space-to-depth stem
+    if (p.kernel == NT_PATCH_S2D) return patch_s2d_launch<E>(a, s);
+    if (p.small) return v2_launch<E, 64, 8, 1, 3, 1, 2, 16, 128>(a, s);
+    return v2_launch<E, 64, 8, 1, 3, 1, 2>(a, s);
+  }
+  if (p.st == 1) return nt_tile_st<E, 1>(p, a, s);
+  if (p.st == 2) return nt_tile_st<E, 2>(p, a, s);
+  return hipErrorInvalidValue;
 }
 
 }  // namespace
 
-// bf16 fast path: C % 64 == 0, ld/co multiples of 8; stats tiles are 256 rows
-bool conv_nt_v2_ok(const ConvArgs& a) {
-  if (a.tap8)   // tap mode (the space-to-depth stem): taps of C = 8 * tap8 channels (tap8 = 2),
-                // weights [Co][ldw >= ceil(KH*KW*C/64)*64]
-    return a.tap8 == 2 && a.st == 1 && a.C == 16 && a.ldx == 16 && a.Co <= 64 && (a.Co % 8) == 0 &&
-           (a.ldy % 8) == 0 && a.ldw >= (a.KH * a.KW * a.C + BK - 1) / BK * BK && (a.ldw % 8) == 0 &&
-           !a.r && !a.r2 && (long)a.N * a.Ho * a.Wo < (1L << 31);
-  return (a.st == 1 || a.st == 2) && (a.C % BK) == 0 && (a.ldx % 8) == 0 && (a.ldw % 8) == 0 && (a.Co % 8) == 0 &&
-         (a.ldy % 8) == 0 && (!a.r || a.ldr % 8 == 0) && (!a.r2 || a.ldr2 % 8 == 0) &&
-         (long)a.N * a.Ho * a.Wo < (1L << 31);   // 32-bit pixel decode
-}
-
-// rows per tile of the v2 config launch_conv_nt_v2 picks (= BN-statistics partial rows).
-// (Measured and rejected: 128 x 128 tiles with a 64 KB ring, two workgroups per CU, for short
-// reductions K <= 512 -- 10-20 % slower than 256-row tiles on the C2 1x1 layers.)
-// 128-row tiles, two workgroups per CU, for the narrow (Co <= 64) layers -- the stem and block1:
-// short reductions whose one-tile-per-CU 256-row launches were latency-bound (stem forward
-// 287 -> 241 us, block1 1x1 / 3x3 layers 4-18 % faster)
-static bool v2_small_tile(const ConvArgs& a) { return a.Co <= 64; }
-
-int conv_nt_v2_rows(const ConvArgs& a) {
-  // the ping-pong kernel writes one partial per wave row (128 rows), the v2 kernels one per tile
-  if (a.Co > 128 && !a.r && !a.r2 && conv_nt_pp_ok(a)) return 128;
-  if (conv_nt_patch_ok(a) || conv_nt_patch_s2d_ok(a)) return 256;
-  return v2_small_tile(a) ? 128 : 256;
-}
-
-// K-concatenated second GEMM on output tiles of <= 128 channels (dense 1x1 rows only)
-bool conv_nt_v2_dual_ok(const ConvArgs& a) {
-  return a.x2 && a.st == 1 && a.sf == 1 && a.KH == 1 && a.KW == 1 && a.pad_h == 0 && a.pad_w == 0 &&
-         a.H == a.Ho && a.W == a.Wo && a.Co <= 128 && a.C2 % BK == 0 && a.ldx2 % 8 == 0 &&
-         a.ldw2 % 8 == 0 && !a.r && !a.r2 && !a.stats && !a.tap8;
-}
-
-template <typename E, int ST>
-hipError_t v2_dispatch(int dtype, const ConvArgs& a, hipStream_t s) {
-  if constexpr (ST == 1) {
-    if (a.x2) {
-      if (!conv_nt_v2_dual_ok(a) || !conv_nt_v2_ok(a)) return hipErrorInvalidValue;
-      if (a.Co > 64) return v2_launch<E, 128, 4, 2, 3, 1, 0, 16, 256, 1>(a, s);
-      return v2_launch<E, 64, 8, 1, 3, 1, 0, 16, 128, 1>(a, s);
-    }
-  }
-  if (ST == 1 && conv_nt_patch_ok(a)) {
-    // 64-channel output tiles with one patch buffer fit 72 KB and 110 VGPRs: two workgroups
-    // per CU hide each other's barrier and fragment-read latency (a 128-channel tile at two
-    // per CU needs <= 128 VGPRs and spilled); Co = 128 runs as two such tiles per patch, the
-    // 128-channel input as two chunks with the patch reloaded between them
-    return patch_launch<E, 64, 8, 1, 1, 3, 2>(a, s);
-  }
-  if (a.Co > 128) {
-    if (conv_nt_pp_ok(a)) return launch_conv_nt_pp(dtype, a, s);
-    return v2_launch<E, 256, 4, 2, 2, ST>(a, s);
-  }
-  if (a.Co > 64) return v2_launch<E, 128, 4, 2, 3, ST>(a, s);
-  if (v2_small_tile(a)) return v2_launch<E, 64, 8, 1, 3, ST, 0, 16, 128>(a, s);
-  return v2_launch<E, 64, 8, 1, 3, ST>(a, s);
-}
-
-template <typename E>
-hipError_t nt_v2_e(int dtype, const ConvArgs& a, hipStream_t s) {
-  if (a.tap8) {
-    if (conv_nt_patch_s2d_ok(a)) return patch_s2d_launch<E>(a, s);
-    if (v2_small_tile(a)) return v2_launch<E, 64, 8, 1, 3, 1, 2, 16, 128>(a, s);
-    return v2_launch<E, 64, 8, 1, 3, 1, 2>(a, s);
-  }
-  if (a.st == 1) return v2_dispatch<E, 1>(dtype, a, s);
-  if (a.st == 2) return v2_dispatch<E, 2>(dtype, a, s);
-  return hipErrorInvalidValue;
-}
-
-hipError_t launch_conv_nt_v2(int dtype, const ConvArgs& a, hipStream_t s) {
-  if (dtype == SEG_F16) return nt_v2_e<f16_t>(dtype, a, s);
-  return nt_v2_e<bf16_t>(dtype, a, s);
+hipError_t launch_conv_nt_tile(int dtype, const ConvNtPlan& p, const ConvArgs& a, hipStream_t s) {
+  if (dtype == SEG_F16) return nt_tile_e<f16_t>(p, a, s);
+  return nt_tile_e<bf16_t>(p, a, s);
 }
 
 // ======================================================================================
@@ -1187,6 +1135,7 @@ hipError_t wg2_launch(const WgradArgs& a, hipStream_t s) {
   constexpr int LDS = STAGES * WBK * (BM + BN) * 2;
   static_assert(LDS <= 160 * 1024, "LDS budget");
   static_assert(STAGES <= 4 && (STAGES < 4 || 2 * (WBK * (BM + BN) / 8 / WG_THREADS) <= 16), "vmcnt");
+  static_assert(LDS == conv_wgrad_v2_lds(BM, BN), "the plan's LDS (conv_select.h)");
   auto kern = conv_wgrad_v2_kernel<E, BM, BN, WMW, WNW, STAGES, WBK>;
   static bool attr = false;
   if (!attr) {
@@ -1200,65 +1149,26 @@ hipError_t wg2_launch(const WgradArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// the v2 tile a plan names (bm, bn in {64, 128, 256})
+template <typename E>
+hipError_t wgrad_v2_e(const ConvWgradPlan& p, const WgradArgs& a, hipStream_t s) {
+  switch (p.bm * 1000 + p.bn) {
+    case 64064: return wg2_launch<E, 64, 64, 4, 2, 3>(a, s);
+    case 64128: return wg2_launch<E, 64, 128, 2, 4, 3>(a, s);
+    case 64256: return wg2_launch<E, 64, 256, 2, 4, 3>(a, s);
+    case 128064: return wg2_launch<E, 128, 64, 4, 2, 3>(a, s);
+    case 128128: return wg2_launch<E, 128, 128, 4, 2, 3>(a, s);
+    case 128256: return wg2_launch<E, 128, 256, 2, 4, 3>(a, s);
+    case 256064: return wg2_launch<E, 256, 64, 8, 1, 3>(a, s);
+    case 256128: return wg2_launch<E, 256, 128, 4, 2, 3>(a, s);
+    case 256256: return wg2_launch<E, 256, 256, 2, 4, 2>(a, s);
+  }
+  return hipErrorInvalidValue;
+}
+
 }  // namespace
 
-bool conv_wgrad_v2_ok(const WgradArgs& a) {
-  return (a.C % 8) == 0 && (a.ldx % 8) == 0 && (a.Co % 8) == 0 && (a.lddy % 8) == 0 &&
-         (long)a.N * a.Ho * a.Wo < (1L << 31) &&
-         (!a.dy2 || (a.Co1 % 8 == 0 && a.Co1 < a.Co && a.lddy2 % 8 == 0));
-}
-
-// tile (BM co x BN cols): the largest the extents fill -- 256 x 256 (wave tiles 128 x 64)
-// keeps LDS fragment traffic below the MFMA time and halves L2 re-reads vs 128 x 256 -- then
-// halved (larger side first) while tiles x pixel splits would leave fewer than 128 workgroups
-// (small outputs such as 256 x 256 1x1 convs: 1 tile x 64 splits = 64 workgroups otherwise).
-// 128, the side stream's workgroup target (wgrad_splits): halving down to 256 workgroups
-// (round 5) gave block2 / head 1 x 1 layers 128 x 128 tiles where 128 x 256 / 256 x 128 now
-// run at the same workgroup count with half the operand re-reads: step +0.53 % (three
-// interleaved pairs, profiles/r06_s30_wgrad_tile_target.txt; 64: +0.27 %)
-void conv_wgrad_v2_tile(int Co, int Ncol, long P, int* bm, int* bn) {
-  int m = Co <= 64 ? 64 : (Co <= 128 ? 128 : 256);
-  int n = Ncol <= 64 ? 64 : (Ncol <= 128 ? 128 : 256);
-  const long maxs = std::min<long>(256, std::max<long>(1, P / 2048));
-  auto blocks = [&]() { return (long)((Co + m - 1) / m) * ((Ncol + n - 1) / n) * maxs; };
-#ifndef WG_TILE_TARGET
-#define WG_TILE_TARGET 128
-#endif
-  while (blocks() < WG_TILE_TARGET) {
-    if (m >= n && m > 64) m /= 2;
-    else if (n > 64) n /= 2;
-    else break;
-  }
-  *bm = m;
-  *bn = n;
-}
-
-hipError_t launch_conv_wgrad_v2(int dtype, const WgradArgs& a, hipStream_t s) {
-  int bm, bn;
-  conv_wgrad_v2_tile(a.Co, a.KH * a.KW * a.C, (long)a.N * a.Ho * a.Wo, &bm, &bn);
-  return launch_conv_wgrad_v2_tile(dtype, a, bm, bn, s);
-}
-
-// explicit tile (bm, bn in {64, 128, 256}); 256 x 256 runs the ping-pong kernel
-template <typename E>
-hipError_t wgrad_v2_tile_e(int dtype, const WgradArgs& a, int bm, int bn, hipStream_t s) {
-  if (bm == 64) {
-    if (bn == 64) return wg2_launch<E, 64, 64, 4, 2, 3>(a, s);
-    if (bn == 128) return wg2_launch<E, 64, 128, 2, 4, 3>(a, s);
-    return wg2_launch<E, 64, 256, 2, 4, 3>(a, s);
-  }
-  if (bm == 128) {
-    if (bn == 64) return wg2_launch<E, 128, 64, 4, 2, 3>(a, s);
-    if (bn == 128) return wg2_launch<E, 128, 128, 4, 2, 3>(a, s);
-    return wg2_launch<E, 128, 256, 2, 4, 3>(a, s);
-  }
-  if (bn == 64) return wg2_launch<E, 256, 64, 8, 1, 3>(a, s);
-  if (bn == 128) return wg2_launch<E, 256, 128, 4, 2, 3>(a, s);
-  if (conv_wgrad_pp_ok(a)) return launch_conv_wgrad_pp(dtype, a, s);
-  return wg2_launch<E, 256, 256, 2, 4, 2>(a, s);
-}
-
-hipError_t launch_conv_wgrad_v2_tile(int dtype, const WgradArgs& a, int bm, int bn, hipStream_t s) {
-  if (dtype == SEG_F16) return wgrad_v2_tile_e<f16_t>(dtype, a, bm, bn, s);
-  return wgrad_v2_tile_e<bf16_t>(dtype, a, bm, bn, s);
+hipError_t launch_conv_wgrad_v2(int dtype, const ConvWgradPlan& p, const WgradArgs& a, hipStream_t s) {
+  if (dtype == SEG_F16) return wgrad_v2_e<f16_t>(p, a, s);
+  return wgrad_v2_e<bf16_t>(p, a, s);
 }

@@ -458,6 +458,40 @@ int alloc_conv(seg_ctx* c, ConvL& L, int N, int H, int W, int ldy = 0) {
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------
+// conv argument builders: shared by the network's launches and the seg_op_conv_* entries
+// ------------------------------------------------------------------------------------------
+// a forward conv of x [N][H][W][ldx] with w [Co][k][k][C] into y [N][Ho][Wo][ldy]
+ConvArgs fwd_conv_args(const void* x, int N, int H, int W, int C, int ldx, const void* w, int Co,
+                       int k, int stride, int rate, int pad_h, int pad_w, int Ho, int Wo, void* y,
+                       int ldy, float* stats) {
+  ConvArgs a{};
+  a.x = x; a.N = N; a.H = H; a.W = W; a.C = C; a.ldx = ldx;
+  a.w = w; a.ldw = k * k * C;
+  a.y = y; a.Ho = Ho; a.Wo = Wo; a.Co = Co; a.ldy = ldy;
+  a.KH = a.KW = k; a.sf = stride; a.st = 1; a.pad_h = pad_h; a.pad_w = pad_w;
+  a.dil = rate; a.stats = stats;
+  return a;
+}
+// the 16-bit stem: 4 x 4 VALID over the space-to-depth image (conv.h), weights wpad [Co][256]
+void fwd_s2d_args(ConvArgs& a, const void* wpad) {
+  a.C = 16; a.ldx = 16; a.tap8 = 2; a.w = wpad; a.ldw = 256;
+  a.KH = a.KW = 4; a.sf = 1; a.pad_h = a.pad_w = 0; a.dil = 1;
+}
+// the weight gradient of that conv from dy [P][lddy]; s2d: the stem's 4 x 4 VALID form (x is
+// the space-to-depth image, C = 16)
+WgradArgs wgrad_conv_args(const void* dy, int lddy, const void* x, int N, int H, int W, int C, int ldx,
+                          int Ho, int Wo, int Co, int k, int stride, int rate, int pad_h, int pad_w,
+                          bool s2d = false) {
+  WgradArgs a{};
+  a.dy = dy; a.lddy = lddy;
+  a.x = x; a.N = N; a.H = H; a.W = W; a.C = C; a.ldx = ldx;
+  a.Ho = Ho; a.Wo = Wo; a.Co = Co;
+  a.KH = a.KW = k; a.sf = stride; a.pad_h = pad_h; a.pad_w = pad_w; a.dil = rate;
+  if (s2d) { a.KH = a.KW = 4; a.sf = 1; a.pad_h = a.pad_w = 0; a.dil = 1; }
+  return a;
+}
+
 // concurrent = the weight gradient runs on the side stream beside the dgrad -> BN chain:
 // at most ~128 workgroups (half the CUs, the chain keeps the other half: 90.4 -> 92.9 img/s
 // on C2 against 512, and half the split-K slab traffic); alone (profiled, single stream,
@@ -467,14 +501,8 @@ int alloc_conv(seg_ctx* c, ConvL& L, int N, int H, int W, int ldy = 0) {
 // 3x3 (9 tiles) 24 splits 188 us, 32 splits (288 workgroups) 266 us; block3 1x1 (4 tiles) 64
 // splits 97 us against the former 2-wave 128 splits 121 us.
 int wgrad_splits(const WgradArgs& a, int dt, bool concurrent = false) {
-  const int ci = a.C, k = a.KH, co = a.Co;   // Co = co_pad; 16 / 4 for the space-to-depth stem
-  int BM = co <= 64 ? 64 : 128;
-  int BN = 128;
-  long P = (long)a.N * a.Ho * a.Wo;
-  if (ci % 8 == 0) conv_wgrad_v2_tile(co, k * k * ci, P, &BM, &BN);
-  long tiles = (long)((co + BM - 1) / BM) * ((k * k * ci + BN - 1) / BN);
-  // the small-channel 3 x 3 patch kernel: the same predicate launch_conv_wgrad dispatches on
-  if (seg_half(dt) && conv_wgrad_patch_ok(a)) tiles = conv_wgrad_patch_blocks(a);
+  const long P = (long)a.N * a.Ho * a.Wo;
+  const long tiles = conv_wgrad_plan(dt, a).split_tiles;   // of the kernel launch_conv_wgrad runs
   // workgroups = tiles x splits <= one wave of the CUs the launch may use; each split >= 32
   // K-steps of 64 pixels beside the dgrad chain, >= 16 alone
   const long target = concurrent ? 128 : 256;
@@ -488,12 +516,9 @@ int wgrad_splits(const WgradArgs& a, int dt, bool concurrent = false) {
 // channels padded to a multiple of 8); the space-to-depth stem is a 4 x 4 VALID conv over 16
 // channels
 WgradArgs wgrad_problem(const ConvL& L, bool s2d) {
-  WgradArgs a{};
-  a.N = L.N; a.H = L.H; a.W = L.W; a.C = s2d ? 16 : L.ci; a.ldx = (a.C + 7) / 8 * 8;
-  a.Ho = L.Ho; a.Wo = L.Wo; a.Co = L.co_pad; a.lddy = (L.co_pad + 7) / 8 * 8;
-  a.KH = a.KW = s2d ? 4 : L.k; a.sf = s2d ? 1 : L.stride; a.dil = s2d ? 1 : L.rate;
-  a.pad_h = s2d ? 0 : L.pad_h; a.pad_w = s2d ? 0 : L.pad_w;
-  return a;
+  const int C = s2d ? 16 : L.ci;
+  return wgrad_conv_args(nullptr, (L.co_pad + 7) / 8 * 8, nullptr, L.N, L.H, L.W, C, (C + 7) / 8 * 8,
+                         L.Ho, L.Wo, L.co_pad, L.k, L.stride, L.rate, L.pad_h, L.pad_w, s2d);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -533,16 +558,10 @@ int conv_forward(Step& S, int li, const Act& x) {
   seg_ctx* c = S.c;
   ConvL& L = c->convs[li];
   L.x = x;
-  ConvArgs a{};
-  a.x = x.p; a.N = x.N; a.H = x.H; a.W = x.W; a.C = x.C; a.ldx = x.ld;
-  a.w = L.w_lp; a.ldw = L.k * L.k * L.ci;
-  a.y = L.y.p; a.Ho = L.Ho; a.Wo = L.Wo; a.Co = L.co; a.ldy = L.y.ld;
-  a.KH = a.KW = L.k; a.sf = L.stride; a.st = 1; a.pad_h = L.pad_h; a.pad_w = L.pad_w;
-  a.dil = L.rate; a.stats = L.stats_part;
-  if (li == c->stem && c->stem_s2d) {   // 4 x 4 VALID over the space-to-depth image
-    a.C = 16; a.ldx = 16; a.tap8 = 2; a.w = c->stem_wpad; a.ldw = 256;
-    a.KH = a.KW = 4; a.sf = 1; a.pad_h = a.pad_w = 0; a.dil = 1;
-  }
+  ConvArgs a = fwd_conv_args(x.p, x.N, x.H, x.W, x.C, x.ld, L.w_lp, L.co, L.k, L.stride, L.rate,
+                             L.pad_h, L.pad_w, L.Ho, L.Wo, L.y.p, L.y.ld, L.stats_part);
+  a.ldw = L.k * L.k * L.ci;   // the weights' row length is the layer's, whatever view x is
+  if (li == c->stem && c->stem_s2d) fwd_s2d_args(a, c->stem_wpad);
   long M = (long)x.N * L.Ho * L.Wo;
   int slot;
   const double esz = c->esz;   // x + w + y, each once
@@ -562,7 +581,7 @@ int conv_forward(Step& S, int li, const Act& x) {
   if (c->bn_infer) return 0;   // is_training=False: the statistics were set for every layer
                                // by one launch at the start of the forward
   const bool sync = c->sync_fn != nullptr;
-  HIPCALL(c, launch_bn_stats_finalize(L.stats_part, M, L.co, conv_nt_stat_rows(S.dt, 0, a), c->stat_scratch,
+  HIPCALL(c, launch_bn_stats_finalize(L.stats_part, M, L.co, conv_nt_plan(S.dt, 0, a).stat_rows, c->stat_scratch,
                                       c->params + L.g_off, L.st, S.s, sync ? c->sync_pack : nullptr));
   if (sync) {
     if (int r = sync_exchange(c, c->sync_pack, 2L * L.co, S.s)) return r;
@@ -851,17 +870,18 @@ int conv_dgrad_dual(Step& S, int li, int li2, const Act& dx, const uint8_t** oma
     return 1;
   ConvArgs a = dgrad_args(c, li, dx, nullptr, nullptr);
   dgrad_dual_args(a, L2.dy.p, L2.dy.ld, L2.co, L2.wt_lp);
-  if (a.st != 1 || a.sf != 1 || a.pad_h || a.pad_w || !conv_nt_pp_ok(a)) return 1;
+  // the ping-pong dual only: a narrow unit input keeps the two data gradients
+  if (a.st != 1 || a.sf != 1 || a.pad_h || a.pad_w || conv_nt_plan(S.dt, 0, a).kernel != NT_PP) return 1;
   if (omask && *omask) {   // stored masked by the consumer's ReLU bits where that launch exists
     a.omask = *omask; a.ldm = a.Co / 8;
-    if (!conv_nt_omask_ok(S.dt, a)) { a.omask = nullptr; *omask = nullptr; }
+    if (!conv_nt_plan(S.dt, 0, a).omask) { a.omask = nullptr; *omask = nullptr; }
   }
   const long M = (long)L.N * L.H * L.W;
   const double gbx = ((double)M * (L.co + L2.co) + (double)(L.co + L2.co) * L.ci + (double)M * L.ci) *
                      c->esz * 1e-9;
   int slot;
   if (int r = prof_begin(c, S.s, 1, li, 2.0 * M * L.ci * (L.co + L2.co) * 1e-9, &slot, gbx)) return r;
-  HIPCALL(c, launch_conv_nt_pp(S.dt, a, S.s));
+  HIPCALL(c, launch_conv_nt(S.dt, 0, a, S.s));
   if (int r = prof_end(c, S.s, slot)) return r;
   return 0;
 }
@@ -911,13 +931,9 @@ int conv_wgrad(Step& S, int li, const Act& x) {
 int conv_wgrad_impl(Step& S, int li, const Act& x) {
   seg_ctx* c = S.c;
   ConvL& L = c->convs[li];
-  WgradArgs a{};
-  a.dy = L.dy.p; a.lddy = L.dy.ld;
-  a.x = x.p; a.N = x.N; a.H = x.H; a.W = x.W; a.C = x.C; a.ldx = x.ld;
-  a.Ho = L.Ho; a.Wo = L.Wo; a.Co = L.co_pad;
-  a.KH = a.KW = L.k; a.sf = L.stride; a.pad_h = L.pad_h; a.pad_w = L.pad_w; a.dil = L.rate;
   const bool s2d = li == c->stem && c->stem_s2d;
-  if (s2d) { a.KH = a.KW = 4; a.sf = 1; a.pad_h = a.pad_w = 0; a.dil = 1; }
+  WgradArgs a = wgrad_conv_args(L.dy.p, L.dy.ld, x.p, x.N, x.H, x.W, x.C, x.ld, L.Ho, L.Wo, L.co_pad,
+                                L.k, L.stride, L.rate, L.pad_h, L.pad_w, s2d);
   // the stem's weight gradient is the last work of the step (its dgrad is skipped): nothing
   // runs beside it, so it takes the whole chip (tools/timeline.py: the compute stream idled
   // ~0.75 ms waiting for it)
@@ -1384,8 +1400,8 @@ bool premask_ok(seg_ctx* c, const Unit& u, const Unit* pred, bool accumulate) {
     return false;
   if (!pred->out.mask || pred->out.C != c->convs[u.c1].ci || c->convs[pred->c3].co != pred->out.C) return false;
   ConvArgs a = dgrad_args(c, u.c1, pred->dout, &u.dpre, nullptr);
-  a.ldm = a.Co / 8;
-  return conv_nt_omask_ok(c->dt, a);
+  a.omask = pred->out.mask; a.ldm = a.Co / 8;
+  return conv_nt_plan(c->dt, 0, a).omask;
 }
 
 // the ReLU bits of pred's output when the data gradient into it (of C channels) may be stored
@@ -1420,7 +1436,7 @@ bool lbf_ok(seg_ctx* c, const Unit& u, bool in_masked) {
   a.x2 = u.z2.p; a.ldx2 = u.z2.ld; a.C2 = L3.ci; a.w2 = c->lbf_h; a.ldw2 = L3.ci;
   a.KH = a.KW = 1; a.sf = 1; a.st = 1; a.dil = 1;
   if (u.kind != SC_CONV && u.dpre.ld != u.dout.ld) return false;
-  return L3.ci > 128 ? conv_nt_pp_ok(a) : conv_nt_v2_ok(a) && conv_nt_v2_dual_ok(a);
+  return conv_nt_plan(c->dt, 0, a).kernel != NT_INVALID;
 }
 
 // the weight gradient of a folded conv3 (on the weight-gradient stream when it is active):
@@ -1444,33 +1460,20 @@ int lbf_wgrad(Step& S, Unit& u, const Act& dyhat) {
   // (the combine is recorded with the BN-backward apply class, lbf_combine)
   const double gbx = (((double)P * L.co + (double)P * L.ci) * c->esz + (double)L.co * L.ci * 4.0) * 1e-9;
   if (int r = prof_begin(c, W.s, 2, li, 2.0 * P * L.co * L.ci * 1e-9, &slot, gbx)) return r;
-  if (L.ci < 256) {   // narrow ci: P1 and G as one launch of the tile shape the v2 heuristic picks
-    WgradArgs a{};
-    a.dy = dyhat.p; a.lddy = dyhat.ld;
-    a.dy2 = y2.p; a.lddy2 = y2.ld; a.Co1 = L.co;
-    a.x = y2.p; a.N = y2.N; a.H = y2.H; a.W = y2.W; a.C = y2.C; a.ldx = y2.ld;
-    a.Ho = L.Ho; a.Wo = L.Wo; a.Co = L.co + L.ci;
-    a.KH = a.KW = 1; a.sf = 1; a.dil = 1;
-    a.splits = wgrad_splits(a, S.dt, c->side_active);
-    a.splits = (int)std::max<long>(1, std::min<long>(a.splits, (long)c->slab_floats / n1));
-    a.out = c->slab;
-    HIPCALL(c, launch_conv_wgrad(S.dt, a, W.s));
-    HIPCALL(c, launch_splitk_reduce(c->slab, a.splits, n1, n1, c->lbf_p1, 0, W.s));
-  } else {
-    // P1 = dyhat^T y2 and G = y2^T y2 as one launch: output rows co.. co + ci - 1 take y2 as dy
-    WgradArgs a{};
-    a.dy = dyhat.p; a.lddy = dyhat.ld;
-    a.dy2 = y2.p; a.lddy2 = y2.ld; a.Co1 = L.co;
-    a.x = y2.p; a.N = y2.N; a.H = y2.H; a.W = y2.W; a.C = y2.C; a.ldx = y2.ld;
-    a.Ho = L.Ho; a.Wo = L.Wo; a.Co = L.co + L.ci;
-    a.KH = a.KW = 1; a.sf = 1; a.dil = 1;
-    a.splits = wgrad_splits(a, S.dt, c->side_active);
-    a.splits = (int)std::max<long>(1, std::min<long>(a.splits, (long)c->slab_floats / ((long)a.Co * a.C)));
-    a.out = c->slab;
-    if (!conv_wgrad_pp_ok(a)) return set_err(&c->err, -EINVAL, "lbf weight gradient %s: shape", L.name.c_str());
-    HIPCALL(c, launch_conv_wgrad_pp(S.dt, a, W.s));
-    HIPCALL(c, launch_splitk_reduce(c->slab, a.splits, n1, n1, c->lbf_p1, 0, W.s));
-  }
+  // P1 = dyhat^T y2 and G = y2^T y2 as one launch: output rows co.. co + ci - 1 take y2 as dy.
+  // Narrow ci: the tile the heuristic picks; ci >= 256: the ping-pong 256 x 256 tile at every
+  // size (the heuristic halves it on small maps)
+  WgradArgs a = wgrad_conv_args(dyhat.p, dyhat.ld, y2.p, y2.N, y2.H, y2.W, y2.C, y2.ld, L.Ho, L.Wo,
+                                L.co + L.ci, 1, 1, 1, 0, 0);
+  a.dy2 = y2.p; a.lddy2 = y2.ld; a.Co1 = L.co;
+  a.splits = wgrad_splits(a, S.dt, c->side_active);
+  a.splits = (int)std::max<long>(1, std::min<long>(a.splits, (long)c->slab_floats / n1));
+  a.out = c->slab;
+  const int tile = L.ci < 256 ? 0 : 256;
+  if (tile && conv_wgrad_plan(S.dt, a, tile, tile).kernel != WG_PP)
+    return set_err(&c->err, -EINVAL, "lbf weight gradient %s: shape", L.name.c_str());
+  HIPCALL(c, launch_conv_wgrad(S.dt, a, W.s, tile, tile));
+  HIPCALL(c, launch_splitk_reduce(c->slab, a.splits, n1, n1, c->lbf_p1, 0, W.s));
   return prof_end(c, W.s, slot);
 }
 
@@ -1545,8 +1548,7 @@ int lbf_backward(Step& S, Unit& u, const Act& dyhat) {
   const long M = (long)L.N * L.H * L.W;
   const double gbx = ((double)M * (co + ci) + (double)co * ci + (double)ci * ci + (double)M * ci) * c->esz * 1e-9;
   if (int r = prof_begin(c, S.s, 1, u.c3, 2.0 * M * ci * co * 1e-9, &slot, gbx)) return r;
-  if (ci > 128) HIPCALL(c, launch_conv_nt_pp(S.dt, a, S.s));
-  else HIPCALL(c, launch_conv_nt_v2(S.dt, a, S.s));
+  HIPCALL(c, launch_conv_nt(S.dt, 0, a, S.s));
   if (int r = prof_end(c, S.s, slot)) return r;
   L.lbf_done = true;
   L.lbf_dyhat = dyhat;
@@ -1857,7 +1859,7 @@ int backward_layers(Step& S) {
     if (pm) {
       ConvArgs a = dgrad_args(c, c->dfd, last.dout, nullptr, nullptr);
       a.omask = pm; a.ldm = a.Co / 8;
-      if (!conv_nt_omask_ok(S.dt, a)) pm = nullptr;
+      if (!conv_nt_plan(S.dt, 0, a).omask) pm = nullptr;
     }
     if (int r = conv_dgrad(S, c->dfd, last.dout, nullptr, nullptr, pm)) return r;
     if (pm) { last.dout_masked = true; ++c->premask_launches; }
@@ -2683,10 +2685,7 @@ int seg_op_conv_fwd(int dtype, const void* x, int N, int H, int W, int C, int ld
                     float* stats, void* stream) {
   int Ho, Wo, ph, pw;
   op_geom(H, W, k, stride, rate, explicit_pad, &Ho, &Wo, &ph, &pw);
-  ConvArgs a{};
-  a.x = x; a.N = N; a.H = H; a.W = W; a.C = C; a.ldx = ldx;
-  a.w = w; a.ldw = k * k * C; a.y = y; a.Ho = Ho; a.Wo = Wo; a.Co = Co; a.ldy = ldy;
-  a.KH = a.KW = k; a.sf = stride; a.st = 1; a.pad_h = ph; a.pad_w = pw; a.dil = rate; a.stats = stats;
+  const ConvArgs a = fwd_conv_args(x, N, H, W, C, ldx, w, Co, k, stride, rate, ph, pw, Ho, Wo, y, ldy, stats);
   hipError_t e = launch_conv_nt(dt_of(dtype), 0, a, (hipStream_t)stream);
   return e == hipSuccess ? 0 : hip_fail(nullptr, e, "seg_op_conv_fwd");
 }
@@ -2695,11 +2694,9 @@ int seg_op_conv_stat_rows(int dtype, int N, int H, int W, int C, int ldx, int Co
                           int stride, int rate, int explicit_pad) {
   int Ho, Wo, ph, pw;   // the ConvArgs seg_op_conv_fwd builds (the kernel choice is shape-dependent)
   op_geom(H, W, k, stride, rate, explicit_pad, &Ho, &Wo, &ph, &pw);
-  ConvArgs a{};
-  a.N = N; a.H = H; a.W = W; a.C = C; a.ldx = ldx; a.ldw = k * k * C; a.Ho = Ho; a.Wo = Wo;
-  a.Co = Co; a.ldy = ldy; a.KH = a.KW = k; a.sf = stride; a.st = 1; a.pad_h = ph; a.pad_w = pw;
-  a.dil = rate;
-  return conv_nt_stat_rows(dt_of(dtype), 0, a);
+  const ConvArgs a = fwd_conv_args(nullptr, N, H, W, C, ldx, nullptr, Co, k, stride, rate, ph, pw, Ho, Wo,
+                                   nullptr, ldy, nullptr);
+  return conv_nt_plan(dt_of(dtype), 0, a).stat_rows;
 }
 
 int seg_op_conv_dgrad(int dtype, const void* dy, int N, int Ho, int Wo, int Co, int lddy,
@@ -2708,12 +2705,7 @@ int seg_op_conv_dgrad(int dtype, const void* dy, int N, int Ho, int Wo, int Co, 
   int ho, wo, ph, pw;
   op_geom(H, W, k, stride, rate, explicit_pad, &ho, &wo, &ph, &pw);
   if (ho != Ho || wo != Wo) return set_err(nullptr, -EINVAL, "dgrad geometry mismatch");
-  const int keff = k + (k - 1) * (rate - 1);
-  ConvArgs a{};
-  a.x = dy; a.N = N; a.H = Ho; a.W = Wo; a.C = Co; a.ldx = lddy;
-  a.w = wt; a.ldw = k * k * Co; a.y = dx; a.Ho = H; a.Wo = W; a.Co = Ci; a.ldy = lddx;
-  a.KH = a.KW = k; a.sf = 1; a.st = stride; a.pad_h = keff - 1 - ph; a.pad_w = keff - 1 - pw;
-  a.dil = rate;
+  const ConvArgs a = dgrad_conv_args(dy, N, Ho, Wo, Co, lddy, wt, Ci, k, stride, rate, ph, pw, H, W, dx, lddx);
   hipError_t e = launch_conv_nt(dt_of(dtype), 0, a, (hipStream_t)stream);
   return e == hipSuccess ? 0 : hip_fail(nullptr, e, "seg_op_conv_dgrad");
 }
@@ -2723,10 +2715,7 @@ int seg_op_conv_dgrad_res(int dtype, const void* dy, int N, int H, int W, int Co
                           const uint8_t* omask, void* stream) {
   if (!r && !omask) return set_err(nullptr, -EINVAL, "dgrad_res: a residual or a mask is required");
   if (omask && Ci % 8) return set_err(nullptr, -EINVAL, "dgrad_res: masked outputs need Ci %% 8 == 0");
-  ConvArgs a{};
-  a.x = dy; a.N = N; a.H = H; a.W = W; a.C = Co; a.ldx = lddy;
-  a.w = wt; a.ldw = Co; a.y = dx; a.Ho = H; a.Wo = W; a.Co = Ci; a.ldy = lddx;
-  a.KH = a.KW = 1; a.sf = 1; a.st = 1; a.dil = 1;
+  ConvArgs a = dgrad_conv_args(dy, N, H, W, Co, lddy, wt, Ci, 1, 1, 1, 0, 0, H, W, dx, lddx);
   if (r) { a.r = r; a.ldr = ldr; }
   if (omask) { a.omask = omask; a.ldm = Ci / 8; }
   hipError_t e = launch_conv_nt(dt_of(dtype), 0, a, (hipStream_t)stream);
@@ -2756,18 +2745,11 @@ int seg_op_conv_dgrad_fused(int dtype, const void* dy, int N, int H, int W, int 
   if (omask) {
     if (Ci % 8) return set_err(nullptr, -EINVAL, "dgrad_fused: masked outputs need Ci %% 8 == 0");
     a.omask = omask; a.ldm = Ci / 8;
-    if (!conv_nt_omask_ok(dt_of(dtype), a))
-      return set_err(nullptr, -EINVAL, "dgrad_fused: no masked launch for this shape");
   }
-  hipError_t e;
-  if (dy2 && Ci > 128) {   // as conv_dgrad_dual: the ping-pong kernel's K-concatenated GEMM
-    if (!conv_nt_pp_ok(a)) return set_err(nullptr, -EINVAL, "dgrad_fused: dual shape not on the ping-pong path");
-    e = launch_conv_nt_pp(dt_of(dtype), a, (hipStream_t)stream);
-  } else {
-    if (dy2 && !(conv_nt_v2_ok(a) && conv_nt_v2_dual_ok(a)))
-      return set_err(nullptr, -EINVAL, "dgrad_fused: dual shape not on the v2 path");
-    e = launch_conv_nt(dt_of(dtype), 0, a, (hipStream_t)stream);
-  }
+  const ConvNtPlan p = conv_nt_plan(dt_of(dtype), 0, a);
+  if (omask && !p.omask) return set_err(nullptr, -EINVAL, "dgrad_fused: no masked launch for this shape");
+  if (dy2 && p.kernel == NT_INVALID) return set_err(nullptr, -EINVAL, "dgrad_fused: %s", p.reason);
+  hipError_t e = launch_conv_nt(dt_of(dtype), 0, a, (hipStream_t)stream);
   return e == hipSuccess ? 0 : hip_fail(nullptr, e, "seg_op_conv_dgrad_fused");
 }
 
@@ -2777,10 +2759,8 @@ int seg_op_conv_wgrad(int dtype, const void* dy, int N, int Ho, int Wo, int Co, 
   int ho, wo, ph, pw;
   op_geom(H, W, k, stride, rate, explicit_pad, &ho, &wo, &ph, &pw);
   if (ho != Ho || wo != Wo) return set_err(nullptr, -EINVAL, "wgrad geometry mismatch");
-  WgradArgs a{};
-  a.dy = dy; a.lddy = lddy; a.x = x; a.N = N; a.H = H; a.W = W; a.C = Ci; a.ldx = ldx;
-  a.Ho = Ho; a.Wo = Wo; a.Co = Co; a.KH = a.KW = k; a.sf = stride; a.pad_h = ph; a.pad_w = pw;
-  a.dil = rate; a.splits = wgrad_splits(a, dt_of(dtype));
+  WgradArgs a = wgrad_conv_args(dy, lddy, x, N, H, W, Ci, ldx, Ho, Wo, Co, k, stride, rate, ph, pw);
+  a.splits = wgrad_splits(a, dt_of(dtype));
   const long n = (long)Co * k * k * Ci;
   if ((int64_t)a.splits * n * 4 > ws_bytes) a.splits = (int)std::max<int64_t>(1, ws_bytes / (n * 4));
   a.out = (float*)workspace;
@@ -2801,16 +2781,15 @@ int seg_op_conv_wgrad_cfg(int dtype, const void* dy, int N, int Ho, int Wo, int 
   int ho, wo, ph, pw;
   op_geom(H, W, k, stride, rate, explicit_pad, &ho, &wo, &ph, &pw);
   if (ho != Ho || wo != Wo) return set_err(nullptr, -EINVAL, "wgrad geometry mismatch");
-  WgradArgs a{};
-  a.dy = dy; a.lddy = lddy; a.x = x; a.N = N; a.H = H; a.W = W; a.C = Ci; a.ldx = ldx;
-  a.Ho = Ho; a.Wo = Wo; a.Co = Co; a.KH = a.KW = k; a.sf = stride; a.pad_h = ph; a.pad_w = pw;
-  a.dil = rate; a.splits = splits;
+  WgradArgs a = wgrad_conv_args(dy, lddy, x, N, H, W, Ci, ldx, Ho, Wo, Co, k, stride, rate, ph, pw);
+  a.splits = splits;
   const long n = (long)Co * k * k * Ci;
   if ((int64_t)splits * n * 4 > ws_bytes) return set_err(nullptr, -EINVAL, "wgrad_cfg: workspace");
-  if (!conv_wgrad_v2_ok(a)) return set_err(nullptr, -EINVAL, "wgrad_cfg: shape not on the v2 path");
+  if (conv_wgrad_plan(dt_of(dtype), a, bm, bn).kernel == WG_INVALID)
+    return set_err(nullptr, -EINVAL, "wgrad_cfg: shape not on the v2 path");
   a.out = (float*)workspace;
   hipStream_t s = (hipStream_t)stream;
-  hipError_t e = launch_conv_wgrad_v2_tile(dt_of(dtype), a, bm, bn, s);
+  hipError_t e = launch_conv_wgrad(dt_of(dtype), a, s, bm, bn);
   if (e == hipSuccess) e = launch_splitk_reduce((float*)workspace, splits, n, n, dw, 0, s);
   return e == hipSuccess ? 0 : hip_fail(nullptr, e, "seg_op_conv_wgrad_cfg");
 }

@@ -10,10 +10,11 @@
 //    consecutive channels of one pixel: a 16-row group's output is one contiguous 512-B store
 //    (ldy = 16). Blocks of 4 waves own 128-row tiles and reduce the tile's per-channel
 //    (sum, M2) BN partials from the fp32 accumulators (two-pass through LDS), the layout the
-//    BN statistics finalize reads (conv_nt_stat_rows = 128).
+//    BN statistics finalize reads (ConvNtPlan::stat_rows = 128).
 //  narrow K (K <= 16, N % 8 == 0): a thread owns 8 output channels (weights in registers) and
 //    walks rows; each row's K inputs are one or two 16-B loads shared by the row's lanes.
 #include "conv.h"
+#include "conv_launch.h"
 
 namespace {
 
@@ -35,7 +36,7 @@ __global__ __launch_bounds__(SK_THREADS) void skinny_narrow_n_kernel(ConvArgs a)
   const E* Wt = (const E*)a.w;
   E* Y = (E*)a.y;
   // weights: lane supplies W[n = lr][k = 32 kb + 8 lq .. + 8], one 16-B load each (rows
-  // 16-B aligned: conv_skinny_ok); round 5: these were 8 two-byte loads each, 128 per lane
+  // 16-B aligned: conv_select.cpp); round 5: these were 8 two-byte loads each, 128 per lane
   // issued before any pixel load (the l1 logits conv 46 us for 67 MB read)
   V wv[16];
   const V vzero = {};
@@ -189,16 +190,16 @@ __global__ __launch_bounds__(SK_THREADS) void skinny_narrow_k_kernel(ConvArgs a)
 }
 
 template <typename E>
-hipError_t skinny_launch(const ConvArgs& a, hipStream_t s) {
+hipError_t skinny_launch(const ConvNtPlan& p, const ConvArgs& a, hipStream_t s) {
   const long M = (long)a.N * a.Ho * a.Wo;
-  if (a.Co <= 16) {
+  if (p.kernel == NT_SKINNY_N) {
     hipLaunchKernelGGL(skinny_narrow_n_kernel<E>, dim3(ceil_div(M, SK_ROWS)), dim3(SK_THREADS), 0, s, a);
   } else {
     // ~4 blocks per CU: every block stages the weight table once, so the grid stays small and
     // each thread walks many rows
     const int per = SK_THREADS / (a.Co / 8);
     const long blocks = std::min<long>(1024, (M + 4L * per - 1) / (4L * per));
-    const int K = a.C <= 8 ? 8 : 16;
+    const int K = p.st;   // the padded K of the plan: 8 or 16
     const size_t lds = (size_t)(K / 2) * a.Co * sizeof(uint32_t);
     if (K == 8) hipLaunchKernelGGL((skinny_narrow_k_kernel<E, 8>), dim3((int)blocks), dim3(SK_THREADS), lds, s, a);
     else hipLaunchKernelGGL((skinny_narrow_k_kernel<E, 16>), dim3((int)blocks), dim3(SK_THREADS), lds, s, a);
@@ -208,21 +209,7 @@ hipError_t skinny_launch(const ConvArgs& a, hipStream_t s) {
 
 }  // namespace
 
-bool conv_skinny_ok(int dtype, int out_f32, const ConvArgs& a) {
-  if (!seg_half(dtype) || out_f32 || a.KH != 1 || a.KW != 1 || a.sf != 1 || a.st != 1 || a.pad_h ||
-      a.pad_w || a.r || a.r2 || a.tap8)
-    return false;
-  if (a.Co <= 16)   // narrow N: 16-B pixel and weight loads, 4-channel stores inside ldy
-    return a.C % 32 == 0 && a.C <= 512 && a.ldx % 8 == 0 && a.ldy >= (a.Co + 3) / 4 * 4 &&
-           a.ldy % 4 == 0 && a.ldw % 8 == 0 && ((uintptr_t)a.w & 15) == 0;
-  // narrow K (data gradient of a narrow conv): no BN statistics; the weight table (K x Co fp32)
-  // fits the block's LDS
-  return a.C <= 16 && a.ldx % 8 == 0 && a.ldx >= (a.C <= 8 ? 8 : 16) && a.Co % 8 == 0 &&
-         a.ldy % 8 == 0 && SK_THREADS % (a.Co / 8) == 0 && a.Co / 8 <= SK_THREADS && a.Co <= 1024 &&
-         !a.stats;
-}
-
-hipError_t launch_conv_skinny(int dtype, const ConvArgs& a, hipStream_t s) {
-  if (dtype == SEG_F16) return skinny_launch<f16_t>(a, s);
-  return skinny_launch<bf16_t>(a, s);
+hipError_t launch_conv_skinny(int dtype, const ConvNtPlan& p, const ConvArgs& a, hipStream_t s) {
+  if (dtype == SEG_F16) return skinny_launch<f16_t>(p, a, s);
+  return skinny_launch<bf16_t>(p, a, s);
 }

@@ -23,6 +23,7 @@
 //  * split-K over pixel strips into fp32 slabs [split][Co][9 C] (reduced by splitk_reduce, the
 //    layout of the other weight-gradient kernels).
 #include "conv.h"
+#include "conv_launch.h"
 
 namespace {
 
@@ -214,21 +215,11 @@ __global__ __launch_bounds__(WP_THREADS, 1) void conv_wgrad_patch_kernel(WgradAr
 
 }  // namespace
 
-// 3 x 3, stride 1, SAME (pad = dilation <= 4), output rows in 64-pixel strips, 64-channel blocks
-// of both Co and C (at most 128 each: the wider layers keep the ping-pong 256 x 256 tiles),
-// operands < 2^31 bytes (32-bit buffer offsets)
-bool conv_wgrad_patch_ok(const WgradArgs& a) {
-  return a.KH == 3 && a.KW == 3 && a.sf == 1 && a.dil >= 1 && a.dil <= 4 && a.pad_h == a.dil &&
-         a.pad_w == a.dil && a.H == a.Ho && a.W == a.Wo && a.Wo % 64 == 0 && a.C % 64 == 0 &&
-         a.Co % 64 == 0 && a.C <= 128 && a.Co <= 128 && a.ldx % 8 == 0 && a.lddy % 8 == 0 &&
-         (long)a.N * a.H * a.W * a.ldx * 2 < (1L << 31) && (long)a.N * a.Ho * a.Wo * a.lddy * 2 < (1L << 31);
-}
-
-int conv_wgrad_patch_blocks(const WgradArgs& a) { return (a.Co / 64) * (a.C / 64); }
-
-hipError_t launch_conv_wgrad_patch(int dtype, const WgradArgs& a, hipStream_t s) {
-  if (!conv_wgrad_patch_ok(a) || a.splits < 1) return hipErrorInvalidValue;
-  const int grid = conv_wgrad_patch_blocks(a) * a.splits;
+// grid = the plan's 64 x 64-channel blocks x splits (shapes: conv_select.cpp)
+hipError_t launch_conv_wgrad_patch(int dtype, const ConvWgradPlan& p, const WgradArgs& a, hipStream_t s) {
+  static_assert(WP_LDS == CONV_WGRAD_PATCH_LDS, "the plan's LDS (conv_select.h)");
+  if (p.kernel != WG_PATCH || a.splits < 1) return hipErrorInvalidValue;
+  const int grid = (a.Co / 64) * (a.C / 64) * a.splits;
   auto launch = [&](auto kern) -> hipError_t {
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, WP_LDS);
     if (e != hipSuccess) return e;

@@ -25,7 +25,8 @@ EXPORTED_SYMBOLS = [
     "seg_profile", "seg_profile_dump",
     "seg_profile_read", "seg_op_conv_fwd", "seg_op_conv_stat_rows", "seg_op_conv_dgrad",
     "seg_op_conv_dgrad_res",
-    "seg_op_conv_wgrad", "seg_op_conv_wgrad_cfg", "seg_op_conv_dgrad_fused", "seg_bbox_labels", "seg_tag_labels",
+    "seg_op_conv_wgrad", "seg_op_conv_wgrad_cfg", "seg_op_conv_dgrad_fused",
+    "seg_op_conv_plan", "seg_op_conv_wgrad_plan", "seg_bbox_labels", "seg_tag_labels",
     "seg_grad_buckets", "seg_stream_wait_bucket", "seg_set_loss_scale", "seg_found_inf",
     "seg_set_bn_sync", "seg_set_bn_inference", "seg_predict", "seg_full_predictions",
     "seg_set_nesterov", "seg_set_defer_stem", "seg_flush_grads", "seg_set_premask", "seg_set_lbf",
@@ -108,6 +109,8 @@ def _load():
                                    vp, vp, i64, vp]),
         "seg_op_conv_wgrad_cfg": (ip, [ip, vp, ip, ip, ip, ip, ip, vp, ip, ip, ip, ip, ip, ip, ip,
                                        ip, vp, vp, i64, ip, ip, ip, vp]),
+        "seg_op_conv_plan": (ip, [ip, ip, ctypes.POINTER(ctypes.c_int), ip, ip, ctypes.c_char_p, ip]),
+        "seg_op_conv_wgrad_plan": (ip, [ip, ctypes.POINTER(ctypes.c_int), ip, ip, ip, ip, ctypes.c_char_p, ip]),
         "seg_op_conv_dgrad_fused": (ip, [ip, vp, ip, ip, ip, ip, ip, vp, ip, ip, ip, vp, ip,
                                          vp, ip, vp, ip, vp, ip, ip, vp, vp, vp]),
         "seg_bbox_labels": (ip, [vp, vp, vp, vp, ip, ip, ip, ip, vp, vp]),

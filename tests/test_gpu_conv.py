@@ -560,9 +560,9 @@ def test_conv_dgrad_residual_masked_ld(cuda, dtype, case, layout):
 def test_conv_dgrad_residual_unaligned_ldr(cuda, dtype):
     """A residual whose row stride is no multiple of 8 elements (ldr = Ci + 4): the 16-byte
     residual reads of the v2 / ping-pong epilogues and the 16-byte LDS-DMA pieces of RQP would
-    read shifted rows. conv_nt_v2_ok turns such a launch away from every 16-bit tile kernel (it
-    runs on the generic one), so the result is correct per the bound; a negative errno would be
-    acceptable too -- shifted data never."""
+    read shifted rows. The kernel selection (csrc/conv_select.cpp) turns such a launch away from
+    every 16-bit tile kernel (it runs on the generic one), so the result is correct per the
+    bound; a negative errno would be acceptable too -- shifted data never."""
     from seg_hip import LIB
     case = (2, 16, 32, 256, 512, True, False)
     N, H, W, Co, Ci, _, _ = case
@@ -677,8 +677,8 @@ def test_conv_dgrad_dual(cuda, dtype, Ci, with_m):
     """dx = dy . wt + dy2 . wt2 in one K-concatenated launch (a projection unit's conv1 and
     shortcut data gradients; the folded conv3 launches): Ci 512 on the ping-pong kernel (ST = 4),
     with and without the consumer's ReLU bits, Ci 128 on the v2 kernel (no masked launch exists
-    there: conv_nt_omask_ok); 630 pixels: two full row tiles and a ragged one; dy and dy2 with
-    different row strides."""
+    there: the plan of such a request is invalid, csrc/conv_select.cpp); 630 pixels: two full
+    row tiles and a ragged one; dy and dy2 with different row strides."""
     from seg_hip import LIB, check
     N, H, W, Co, Co2 = 2, 15, 21, 256, 256
     M = N * H * W

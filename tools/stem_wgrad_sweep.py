@@ -4,7 +4,7 @@ The stem (7 x 7 stride 2 over 3 channels) runs as a 4 x 4 VALID conv over the 16
 space-to-depth image: dy [4, 512, 1024, 64], x [4, 515, 1027, 16]. The op entry has no VALID
 4 x 4 geometry, so the sweep runs the SAME-padded one (x [4, 512, 1024, 16]: the same gather per
 output pixel, a one-pixel border of out-of-range taps); the library's own choice is
-the v2 kernel at 64 x 256 with 256 splits (conv_wgrad_v2_tile, wgrad_splits). Prints us per
+the v2 kernel at 64 x 256 with 256 splits (conv_wgrad_plan, wgrad_splits). Prints us per
 launch (weight-gradient kernel + split-K reduce) for each (bm, bn, splits)."""
 import os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

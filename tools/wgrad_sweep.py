@@ -1,7 +1,7 @@
 """Tile / split sweep of the v2 weight-gradient kernel on the small-channel C2 layers (GPU box):
     python tools/wgrad_sweep.py [layer ...]   (layers from tools/op_bench.py SHAPES)
 For every (bm, bn, splits) it times kernel + fixed-order split-K reduce (HIP events, 10 reps)
-and prints the default choice (conv_wgrad_v2_tile + wgrad_splits' full-chip target) beside the
+and prints the default choice (conv_wgrad_plan + wgrad_splits' full-chip target) beside the
 best one."""
 import ctypes
 import os
