@@ -43,7 +43,7 @@ struct BnBwdArgs {
   void* dyhat; int lddyhat;        // optional masked gradient (T)
   const float* dzscale;            // optional per-channel factor applied to dz
   // optional per-channel term added to dz before the gate (8-wide masked path only): the
-  // constant part of a data gradient whose producer left it out (net.cpp, linear BN-backward
+  // constant part of a data gradient whose producer left it out (net_layers.cpp, linear BN-backward
   // fold of the consumer's expansion conv)
   const float* dshift;
   int reduce_dyhat;                // the reduce (not the apply) stores the gated gradient in dyhat

@@ -1,4 +1,4 @@
-// Linear BN-backward fold for expansion 1 x 1 convolutions (net.cpp, unit_backward).
+// Linear BN-backward fold for expansion 1 x 1 convolutions (net_layers.cpp lbf_*; net_step.cpp, unit_backward).
 //
 // The training BN backward of a bottleneck's conv3 (reference: slim BN as normalizer_fn,
 // models/resnet50_extended_model_hierarchical.py:298-339; the gradient TF derives for

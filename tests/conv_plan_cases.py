@@ -1,7 +1,7 @@
 """The argument tuples of the conv kernel-selection tests (tests/test_conv_plan.py) and of the
 generator of their parent fixture (tests/golden/make_conv_plan_fixture.py): every request is the
 scalar fields of ConvArgs / WgradArgs in declaration order (csrc/conv_args.h) plus pointer flags,
-built as csrc/net.cpp builds them (fwd_conv_args, dgrad_conv_args, wgrad_conv_args, the
+built as csrc/net_layers.cpp builds them (fwd_conv_args, dgrad_conv_args, wgrad_conv_args, the
 space-to-depth stem rewrite, strides as alloc_conv pads them). Deterministic, no GPU."""
 from oracle.tfseg import SegConfig, build_specs, psp_grids, resnet_units
 
@@ -12,7 +12,7 @@ F_RES, F_RES2, F_STATS, F_MASK, F_DUAL = 1, 2, 4, 8, 16
 
 
 def geom(H, W, k, stride, rate, explicit_pad):
-    """conv_geom of csrc/net.cpp: (Ho, Wo, pad_h, pad_w)"""
+    """conv_geom of csrc/net_build.cpp: (Ho, Wo, pad_h, pad_w)"""
     keff = k + (k - 1) * (rate - 1)
     if explicit_pad:
         return (H - 1) // stride + 1, (W - 1) // stride + 1, (keff - 1) // 2, (keff - 1) // 2

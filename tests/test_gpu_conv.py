@@ -354,7 +354,7 @@ def test_conv_wgrad(cuda, dtype, case):
     from seg_hip import LIB, check
     N, H, W, Ci, Co, k, s, r, ep = case
     # Co % 8 != 0 (the logits convs: 14 / 7 / 3 classes): the runtime pads the gradient's
-    # channels and the weight-gradient rows to a multiple of 16 with zeros (net.cpp conv_wgrad,
+    # channels and the weight-gradient rows to a multiple of 16 with zeros (net_layers.cpp conv_wgrad,
     # co_pad); the padded rows must come out zero
     co_pad = Co if Co % 8 == 0 else (Co + 15) // 16 * 16
     x, w = _tensors(case)
