@@ -16,6 +16,7 @@
 // into fp32 slabs, reduced in a fixed order by splitk_reduce (bitwise reproducible).
 #include "conv.h"
 #include "conv_launch.h"
+#include "conv_tile.h"
 
 namespace {
 
@@ -25,8 +26,6 @@ template <typename T> struct MmaT;
 template <> struct MmaT<bf16_t> { static constexpr int BK = 64; };
 template <> struct MmaT<f16_t> { static constexpr int BK = 64; };
 template <> struct MmaT<float> { static constexpr int BK = 32; };
-
-__device__ __forceinline__ int swz(int row, int ch) { return ch ^ ((row >> 1) & 7); }
 
 template <typename TO> __device__ __forceinline__ void store_out(TO* p, float v);
 template <> __device__ __forceinline__ void store_out<float>(float* p, float v) { *p = v; }

@@ -30,6 +30,7 @@
 //    in place (RQP, PERSIST = 3); two residuals or other shapes run one tile per workgroup.
 #include "conv.h"
 #include "conv_launch.h"
+#include "conv_tile.h"
 #include <cstdlib>
 
 #ifdef PP_DBG_TIMING
@@ -81,8 +82,6 @@ constexpr int PBK = 64;                    // 16-bit K-elements per K-tile (128-
 constexpr int HALF = 128 * 128;            // one half-tile: 128 rows x 128 B
 constexpr int BUF = 4 * HALF;              // A0 A1 B0 B1
 constexpr int PP_LDS = 2 * BUF;            // 128 KB
-
-__device__ __forceinline__ int swz(int row, int ch) { return ch ^ ((row >> 1) & 7); }
 
 template <typename E> __device__ __forceinline__ E lo16(uint32_t w) {
   const uint16_t b = (uint16_t)(w & 0xffffu);
@@ -150,8 +149,7 @@ __device__ __forceinline__ void conv_nt_pp_body(const ConvArgs& a) {
   // XCD-aware bijective remap of t (XCD = t % 8 = b % 8) gives each XCD a contiguous run of
   // tiles, n fastest, so blocks sharing an A panel share an L2
   auto tile_of = [&](int t, int& mt_, int& nt_) {
-    const int xcd = t & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (t >> 3);
+    const int wg = xcd_tile(t, nwg);
     mt_ = wg / ntiles;
     nt_ = wg - mt_ * ntiles;
   };
@@ -863,17 +861,10 @@ hipError_t pp_launch(const ConvArgs& a, hipStream_t s) {
   // two K-tile buffers (the epilogue stages through buffer 1; RQP: the residual tile)
   constexpr int LDS = PP_LDS;
   static_assert(LDS == CONV_NT_PP_LDS, "the plan's LDS (conv_select.h)");
-  auto kern = conv_nt_pp_kernel<E, ST, PERSIST>;
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) return e;
-    attr = true;
-  }
   const long M = (long)a.N * a.Ho * a.Wo;
   const int nwg = ceil_div(M, 256) * ceil_div(a.Co, 256);
-  hipLaunchKernelGGL(kern, dim3(PERSIST == 1 || PERSIST == 3 ? pp_grid(nwg) : nwg), dim3(PP_THREADS), LDS, s, a);
-  return hipGetLastError();
+  return launch_lds<conv_nt_pp_kernel<E, ST, PERSIST>>(dim3(PERSIST == 1 || PERSIST == 3 ? pp_grid(nwg) : nwg),
+                                                       dim3(PP_THREADS), LDS, s, a);
 }
 
 // the instantiation a plan names: ST (0 dense 1 x 1 rows, 4 dense rows + the second GEMM, 1 / 2
@@ -951,10 +942,7 @@ __device__ __forceinline__ void conv_wgrad_pp_body(const WgradArgs& a) {
   const int Ncol = a.KH * a.KW * a.C;
   const int P = a.N * a.Ho * a.Wo;
   const int mtn = (a.Co + BM - 1) / BM, ntn = (Ncol + BN - 1) / BN;
-  const int nwg = mtn * ntn * a.splits;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int wg = xcd_tile(blockIdx.x, mtn * ntn * a.splits);
   const int split = wg / (mtn * ntn);
   const int rem = wg - split * mtn * ntn;
   const int nt_ = rem / mtn, mt_ = rem - nt_ * mtn;
@@ -1284,27 +1272,27 @@ __global__ __launch_bounds__(PP_THREADS, 1) void conv_wgrad_pp_kernel(WgradArgs 
   conv_wgrad_pp_body<E, FAST>(a);
 }
 
+template <typename E, int FAST>
+hipError_t wgrad_pp_launch(const WgradArgs& a, hipStream_t s) {
+  static_assert(WPP_LDS == CONV_WGRAD_PP_LDS, "the plan's LDS (conv_select.h)");
+  const int Ncol = a.KH * a.KW * a.C;
+  const int nwg = ceil_div(a.Co, 256) * ceil_div(Ncol, 256) * a.splits;
+  return launch_lds<conv_wgrad_pp_kernel<E, FAST>>(dim3(nwg), dim3(PP_THREADS), WPP_LDS, s, a);
+}
+
+// p.fast: 2 strip order, 1 Wo >= 64, 0 any width (conv_select.cpp)
+template <typename E>
+hipError_t wgrad_pp_e(const ConvWgradPlan& p, const WgradArgs& a, hipStream_t s) {
+  if (p.fast == 2) return wgrad_pp_launch<E, 2>(a, s);
+  if (p.fast == 1) return wgrad_pp_launch<E, 1>(a, s);
+  return wgrad_pp_launch<E, 0>(a, s);
+}
+
 }  // namespace
 
 hipError_t launch_conv_wgrad_pp(int dtype, const ConvWgradPlan& p, const WgradArgs& a, hipStream_t s) {
-  const int Ncol = a.KH * a.KW * a.C;
-  static_assert(WPP_LDS == CONV_WGRAD_PP_LDS, "the plan's LDS (conv_select.h)");
-  const int nwg = ceil_div(a.Co, 256) * ceil_div(Ncol, 256) * a.splits;
-  auto launch = [&](auto kern) -> hipError_t {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, WPP_LDS);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(PP_THREADS), WPP_LDS, s, a);
-    return hipGetLastError();
-  };
-  // p.fast: 2 strip order, 1 Wo >= 64, 0 any width (conv_select.cpp)
-  if (dtype == SEG_F16) {
-    if (p.fast == 2) return launch(conv_wgrad_pp_kernel<f16_t, 2>);
-    if (p.fast == 1) return launch(conv_wgrad_pp_kernel<f16_t, 1>);
-    return launch(conv_wgrad_pp_kernel<f16_t, 0>);
-  }
-  if (p.fast == 2) return launch(conv_wgrad_pp_kernel<bf16_t, 2>);
-  if (p.fast == 1) return launch(conv_wgrad_pp_kernel<bf16_t, 1>);
-  return launch(conv_wgrad_pp_kernel<bf16_t, 0>);
+  if (dtype == SEG_F16) return wgrad_pp_e<f16_t>(p, a, s);
+  return wgrad_pp_e<bf16_t>(p, a, s);
 }
 
 #ifdef NT_DBG_TIMING

@@ -99,7 +99,7 @@ ConvNtPlan nt_invalid(const char* why) {
   return p;
 }
 
-// conv_nt_v2_kernel<E, BN, WMW, WNW, STAGES, ST, T8, MF, BM, DU>: BN 256 runs 2 stages, 128 and
+// conv_nt_v2_kernel<E, BN, WMW, WNW, STAGES, ST, T8, BM, DU>: BN 256 runs 2 stages, 128 and
 // 64 run 3; LDS = max(the stage ring, the epilogue staging of BM rows)
 ConvNtPlan nt_v2(const ConvArgs& a, int kernel, int bn, int bm, int st, int tap8) {
   ConvNtPlan p{};

@@ -15,6 +15,7 @@
 //    mean) for the fused batch-norm.
 #include "conv.h"
 #include "conv_launch.h"
+#include "conv_tile.h"
 #include <algorithm>
 #include <cstdlib>
 
@@ -28,62 +29,24 @@ namespace {
 constexpr int V2_THREADS = 512;
 constexpr int BK = 64;     // bf16 elements per K-step (128 B per row)
 
-__device__ __forceinline__ int swz(int row, int ch) { return ch ^ ((row >> 1) & 7); }
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else if constexpr (N == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-  else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-  else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  else if constexpr (N == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-  else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  else if constexpr (N == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-  else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-  else if constexpr (N == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-  else static_assert(N < 0, "unsupported vmcnt");
-}
-
-__device__ __forceinline__ void glds16(const void* src, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-template <int TO_F32>
-struct OutT;
-template <> struct OutT<0> { typedef bf16_t T; };
-template <> struct OutT<1> { typedef float T; };
-
 // BM = 256; waves laid out WMW (M) x WNW (N); STAGES-deep ring of 64-deep K-steps.
 // (Measured and rejected: splitting each stage into two 32-deep units refilled one phase
 // after their last read -- 1.5 K-steps of prefetch instead of 1 -- ran 5-8 % slower: the
-// extra barrier per K-step costs more than the deeper prefetch gains.)
-template <int MF> struct AccOf;
-template <> struct AccOf<16> { typedef f32x4_t T; static constexpr int N = 4; };
-
-// MF: MFMA shape (16: v_mfma_f32_16x16x32_bf16). A v_mfma_f32_32x32x16_bf16 main loop with
-// fragments double-buffered across k16-steps was measured 5-9 % slower on the C2 layer shapes
-// and removed; the epilogue keeps the shape-generic (row_of / col_of) accumulator walk.
+// extra barrier per K-step costs more than the deeper prefetch gains; a
+// v_mfma_f32_32x32x16_bf16 main loop with fragments double-buffered across k16-steps, 5-9 %
+// slower on the C2 layer shapes.)
 // DU: dense 1x1 rows plus a K-concatenated second GEMM (x2, w2), the ping-pong kernel's ST = 4
 // for output tiles of <= 128 channels (csrc/lbf.h: the folded conv3 data gradient of block1-2)
-template <typename E, int BN, int WMW, int WNW, int STAGES, int ST, int T8 = 0, int MF = 16, int BM_ = 256,
-          int DU = 0>
-__global__ __launch_bounds__(V2_THREADS, BM_ == 256 ? 1 : 2) void conv_nt_v2_kernel(ConvArgs a) {
+template <typename E, int BN, int WMW, int WNW, int STAGES, int ST, int T8 = 0, int BM = 256, int DU = 0>
+__global__ __launch_bounds__(V2_THREADS, BM == 256 ? 1 : 2) void conv_nt_v2_kernel(ConvArgs a) {
   typedef typename Half<E>::V V;
   const E* zero = (const E*)g_zero16;
-  constexpr int BM = BM_;
   constexpr int WM = BM / WMW, WN = BN / WNW;
-  constexpr int FM = WM / MF, FN = WN / MF;
-  constexpr int NA = AccOf<MF>::N;   // accumulator elements per lane per fragment
-  typedef typename AccOf<MF>::T acc_t;
+  constexpr int FM = WM / 16, FN = WN / 16;     // v_mfma_f32_16x16x32 fragments per wave
   constexpr int AI = BM * 8 / V2_THREADS;       // A glds per lane per K-step (4)
   constexpr int BI = BN * 8 / V2_THREADS;       // B glds per lane per K-step
   constexpr int LPK = AI + BI;
   constexpr int STAGE_BYTES = (BM + BN) * 128;
-  constexpr int EPI_COLS = 64;                  // epilogue chunk width (fp32 staging)
-  constexpr int EPI_LD = EPI_COLS + 4;          // padded fp32 row
   constexpr int LDS_BYTES = STAGES * STAGE_BYTES > BM * EPI_LD * 4 ? STAGES * STAGE_BYTES : BM * EPI_LD * 4;
   static_assert(WMW * WNW == 8, "8 waves");
   static_assert(BI >= 1, "BN >= 64");
@@ -98,12 +61,8 @@ __global__ __launch_bounds__(V2_THREADS, BM_ == 256 ? 1 : 2) void conv_nt_v2_ker
   const long M = (long)a.N * a.Ho * a.Wo;
   const int mtiles = (int)((M + BM - 1) / BM);
   const int ntiles = (a.Co + BN - 1) / BN;
-  // XCD-aware bijective remap: blocks dealt round-robin over 8 XCDs; give each XCD a
-  // contiguous run of tiles (n fastest) so blocks sharing an A panel share an L2
-  const int nwg = mtiles * ntiles;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  // tiles n fastest, so blocks sharing an A panel share an XCD's L2
+  const int wg = xcd_tile(blockIdx.x, mtiles * ntiles);
   const int mt = wg / ntiles, nt = wg - mt * ntiles;
   const long m0 = (long)mt * BM;
   const int n0 = nt * BN;
@@ -203,23 +162,15 @@ __global__ __launch_bounds__(V2_THREADS, BM_ == 256 ? 1 : 2) void conv_nt_v2_ker
     }
   };
 
-  acc_t acc[FM][FN];
+  f32x4_t acc[FM][FN];
 #pragma unroll
   for (int i = 0; i < FM; ++i)
 #pragma unroll
     for (int j = 0; j < FN; ++j)
 #pragma unroll
-      for (int k = 0; k < NA; ++k) acc[i][j][k] = 0.f;
-  // accumulator element (i, j, k) -> tile row / column
-  auto row_of = [&](int i, int k) {
-    if constexpr (MF == 16) return wm * WM + i * 16 + lq * 4 + k;
-    else return wm * WM + i * 32 + (k >> 2) * 8 + (lane >> 5) * 4 + (k & 3);
-  };
-  auto col_of = [&](int j) {
-    if constexpr (MF == 16) return wn * WN + j * 16 + lr;
-    else return wn * WN + j * 32 + (lane & 31);
-  };
-  const bool col_writer = MF == 16 ? lq == 0 : lane < 32;   // one lane per column after merges
+      for (int k = 0; k < 4; ++k) acc[i][j][k] = 0.f;
+  const AccLane<WM, WN> L{wm, wn, lr, lq};   // accumulator element (i, j, k) -> tile row / column
+  const bool col_writer = lq == 0;           // one lane per column after merges
 
   // one K-step of MFMAs; the next stage's LDS-DMA is issued in two parts, one ahead of each
   // 32-deep k-substep, so its issue cost spreads over the MFMA stream
@@ -269,68 +220,14 @@ __global__ __launch_bounds__(V2_THREADS, BM_ == 256 ? 1 : 2) void conv_nt_v2_ker
     const int nkb = kb + STAGES - 1 < nk ? kb + STAGES - 1 : -1;
     compute(kb % STAGES, nkb, (kb + STAGES - 1) % STAGES);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt<0>();
   __builtin_amdgcn_s_barrier();
 
   // ---- epilogue ----
   const int rows_valid = (int)((M - m0) < BM ? (M - m0) : BM);
   float* red = (float*)smem;          // [WMW][BN] column partials
   if (a.stats && rows_valid == BM) {
-    // full tile, one pass over the accumulators: per lane and column, (sum, M2) of its 4*FM
-    // rows from (sum, sum of squares); then Chan merges of equal-count groups over the lane
-    // groups (shfl 16, 32) and the WMW waves (LDS), fixed order
-    float2* red2 = (float2*)smem;     // [WMW][BN] (sum, M2)
-    constexpr float NL = (float)(NA * FM);   // rows per lane
-    float sj[FN], mj[FN];
-#pragma unroll
-    for (int j = 0; j < FN; ++j) {
-      float sm = 0.f, sq = 0.f;
-#pragma unroll
-      for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int k = 0; k < NA; ++k) {
-          const float x = acc[i][j][k];
-          sm += x;
-          sq = __builtin_fmaf(x, x, sq);
-        }
-      sj[j] = sm;
-      mj[j] = fmaxf(sq - sm * sm * (1.f / NL), 0.f);
-    }
-    float n = NL;
-#pragma unroll
-    for (int o = MF; o <= 32; o <<= 1) {   // lanes holding other rows of the same column
-#pragma unroll
-      for (int j = 0; j < FN; ++j) {
-        const float s2 = __shfl_xor(sj[j], o, 64), m2 = __shfl_xor(mj[j], o, 64);
-        const float d = (s2 - sj[j]) / n;
-        mj[j] = mj[j] + m2 + d * d * (0.5f * n);
-        sj[j] += s2;
-      }
-      n *= 2.f;
-    }
-    if (col_writer)
-#pragma unroll
-      for (int j = 0; j < FN; ++j) red2[wm * BN + col_of(j)] = make_float2(sj[j], mj[j]);
-    __syncthreads();
-    if (wm == 0 && col_writer) {
-#pragma unroll
-      for (int j = 0; j < FN; ++j) {
-        const int c = col_of(j);
-        float2 t = red2[c];
-        float nt = (float)WM;
-#pragma unroll
-        for (int w = 1; w < WMW; ++w) {
-          const float2 u = red2[w * BN + c];
-          const float d = u.x / (float)WM - t.x / nt;
-          t.y = t.y + u.y + d * d * (nt * (float)WM / (nt + (float)WM));
-          t.x += u.x;
-          nt += (float)WM;
-        }
-        if (n0 + c < a.Co)   // one (sum, M2) per BM-row tile (ConvNtPlan::stat_rows)
-          *(float2*)(a.stats + 2 * ((size_t)mt * a.Co + n0 + c)) = t;
-      }
-    }
-    __syncthreads();
+    tile_stats_full<BN, WMW, true>(a, acc, smem, L, mt, n0);
   } else if (a.stats) {
     // partial tile: two passes with row masks, from the fp32 accumulators:
     // column sums over the wave's rows -> lane groups (shfl) -> the WMW waves (LDS)
@@ -341,19 +238,19 @@ __global__ __launch_bounds__(V2_THREADS, BM_ == 256 ? 1 : 2) void conv_nt_v2_ker
 #pragma unroll
       for (int i = 0; i < FM; ++i)
 #pragma unroll
-        for (int k = 0; k < NA; ++k) v += row_of(i, k) < rows_valid ? acc[i][j][k] : 0.f;
+        for (int k = 0; k < 4; ++k) v += L.row(i, k) < rows_valid ? acc[i][j][k] : 0.f;
 #pragma unroll
-      for (int o = MF; o <= 32; o <<= 1) v += __shfl_xor(v, o, 64);
+      for (int o = 16; o <= 32; o <<= 1) v += __shfl_xor(v, o, 64);
       cs[j] = v;
     }
     if (col_writer)
 #pragma unroll
-      for (int j = 0; j < FN; ++j) red[wm * BN + col_of(j)] = cs[j];
+      for (int j = 0; j < FN; ++j) red[wm * BN + L.col(j)] = cs[j];
     __syncthreads();
     float mean[FN], tot[FN];
 #pragma unroll
     for (int j = 0; j < FN; ++j) {
-      const int c = col_of(j);
+      const int c = L.col(j);
       float t = 0.f;
 #pragma unroll
       for (int w = 0; w < WMW; ++w) t += red[w * BN + c];
@@ -366,23 +263,23 @@ __global__ __launch_bounds__(V2_THREADS, BM_ == 256 ? 1 : 2) void conv_nt_v2_ker
 #pragma unroll
       for (int i = 0; i < FM; ++i)
 #pragma unroll
-        for (int k = 0; k < NA; ++k) {
+        for (int k = 0; k < 4; ++k) {
           const float d = acc[i][j][k] - mean[j];
-          v += row_of(i, k) < rows_valid ? d * d : 0.f;
+          v += L.row(i, k) < rows_valid ? d * d : 0.f;
         }
 #pragma unroll
-      for (int o = MF; o <= 32; o <<= 1) v += __shfl_xor(v, o, 64);
+      for (int o = 16; o <= 32; o <<= 1) v += __shfl_xor(v, o, 64);
       cs[j] = v;
     }
     __syncthreads();
     if (col_writer)
 #pragma unroll
-      for (int j = 0; j < FN; ++j) red[wm * BN + col_of(j)] = cs[j];
+      for (int j = 0; j < FN; ++j) red[wm * BN + L.col(j)] = cs[j];
     __syncthreads();
     if (wm == 0 && col_writer) {
 #pragma unroll
       for (int j = 0; j < FN; ++j) {
-        const int c = col_of(j);
+        const int c = L.col(j);
         float t = 0.f;
 #pragma unroll
         for (int w = 0; w < WMW; ++w) t += red[w * BN + c];
@@ -392,77 +289,22 @@ __global__ __launch_bounds__(V2_THREADS, BM_ == 256 ? 1 : 2) void conv_nt_v2_ker
     }
     __syncthreads();
   }
-  // coalesced stores: fp32 tile staged through LDS 64 columns at a time, 16 B per lane
-  float* stage = (float*)smem;
-  E* Y = (E*)a.y;
-  const E* R1 = (const E*)a.r;
-  const E* R2 = (const E*)a.r2;
-  const int s_rl = tid >> 3, s_cc = tid & 7;   // store phase: row lane (0..63), 8-col chunk
-#pragma unroll
-  for (int pass = 0; pass < BN / EPI_COLS; ++pass) {
-    const int cbase = pass * EPI_COLS;
-    if (wn * WN + WN > cbase && wn * WN < cbase + EPI_COLS) {
-#pragma unroll
-      for (int j = 0; j < FN; ++j) {
-        const int col = col_of(j);
-        if (col >= cbase && col < cbase + EPI_COLS) {
-#pragma unroll
-          for (int i = 0; i < FM; ++i)
-#pragma unroll
-            for (int k = 0; k < NA; ++k) stage[row_of(i, k) * EPI_LD + (col - cbase)] = acc[i][j][k];
-        }
-      }
-    }
-    __syncthreads();
-    const int n = n0 + cbase + s_cc * 8;
-    if (n < a.Co) {   // Co % 8 == 0 on this path
-#pragma unroll
-      for (int rr = 0; rr < BM / 64; ++rr) {
-        const int row = s_rl + 64 * rr;
-        const long m = m0 + row;
-        if (m < M) {
-          const float* sp = stage + row * EPI_LD + s_cc * 8;
-          const float4 v0 = *(const float4*)sp, v1 = *(const float4*)(sp + 4);
-          float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-          if (R1) {
-            float u[8];
-            Vec8<E>::load(R1 + (size_t)m * a.ldr + n, u);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] += u[e];
-          }
-          if (R2) {
-            float u[8];
-            Vec8<E>::load(R2 + (size_t)m * a.ldr2 + n, u);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] += u[e];
-          }
-          store8_nt(Y + (size_t)m * a.ldy + n, v);
-        }
-      }
-    }
-    __syncthreads();
-  }
+  tile_store_staged<E, BM, BN, true>(a, acc, smem, L, n0, [&](int row, long& m) {
+    m = m0 + row;
+    return m < M;
+  });
 }
 
-template <typename E, int BN, int WMW, int WNW, int STAGES, int ST, int T8 = 0, int MF = 16, int BM = 256,
-          int DU = 0>
+template <typename E, int BN, int WMW, int WNW, int STAGES, int ST, int T8 = 0, int BM = 256, int DU = 0>
 hipError_t v2_launch(const ConvArgs& a, hipStream_t s) {
   constexpr int STAGE_BYTES = (BM + BN) * 128;
-  constexpr int EPI = BM * (64 + 4) * 4;
+  constexpr int EPI = BM * EPI_LD * 4;
   constexpr int LDS = STAGES * STAGE_BYTES > EPI ? STAGES * STAGE_BYTES : EPI;
   static_assert(LDS <= 160 * 1024, "LDS budget");
   static_assert(LDS == conv_nt_v2_lds(BM, BN), "the plan's LDS (conv_select.h)");
-  auto kern = conv_nt_v2_kernel<E, BN, WMW, WNW, STAGES, ST, T8, MF, BM, DU>;
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) return e;
-    attr = true;
-  }
   long M = (long)a.N * a.Ho * a.Wo;
   int nwg = ceil_div(M, BM) * ceil_div(a.Co, BN);
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(V2_THREADS), LDS, s, a);
-  return hipGetLastError();
+  return launch_lds<conv_nt_v2_kernel<E, BN, WMW, WNW, STAGES, ST, T8, BM, DU>>(dim3(nwg), dim3(V2_THREADS), LDS, s, a);
 }
 
 // ======================================================================================
@@ -495,117 +337,16 @@ __device__ __forceinline__ void patch_epilogue(const ConvArgs& a, f32x4_t (&acc)
                                                char* smem, int pt, int n0, int nimg, int ty0, int tx0) {
   constexpr int BM = PT_H * PT_W;
   constexpr int WM = BM / WMW, WN = BN / WNW;
-  constexpr int FM = WM / 16, FN = WN / 16;
-  constexpr int EPI_COLS = 64, EPI_LD = EPI_COLS + 4;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave / WNW, wn = wave % WNW;
-  const int lr = lane & 15, lq = lane >> 4;
-  auto row_of = [&](int i, int k) { return wm * WM + i * 16 + lq * 4 + k; };
-  auto col_of = [&](int j) { return wn * WN + j * 16 + lr; };
-  if (a.stats) {
-    // as conv_nt_v2_kernel's full-tile path: per lane (sum, M2) of its 4 * FM rows, Chan
-    // merges over the lane groups (shfl 16, 32) and the WMW waves (LDS), fixed order
-    float2* red2 = (float2*)smem;
-    constexpr float NL = (float)(4 * FM);
-    float sj[FN], mj[FN];
-#pragma unroll
-    for (int j = 0; j < FN; ++j) {
-      float sm = 0.f, sq = 0.f;
-#pragma unroll
-      for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const float x = acc[i][j][k];
-          sm += x;
-          sq = __builtin_fmaf(x, x, sq);
-        }
-      sj[j] = sm;
-      mj[j] = fmaxf(sq - sm * sm * (1.f / NL), 0.f);
-    }
-    float n = NL;
-#pragma unroll
-    for (int o = 16; o <= 32; o <<= 1) {
-#pragma unroll
-      for (int j = 0; j < FN; ++j) {
-        const float s2 = __shfl_xor(sj[j], o, 64), m2 = __shfl_xor(mj[j], o, 64);
-        const float d = (s2 - sj[j]) / n;
-        mj[j] = mj[j] + m2 + d * d * (0.5f * n);
-        sj[j] += s2;
-      }
-      n *= 2.f;
-    }
-    if (lq == 0)
-#pragma unroll
-      for (int j = 0; j < FN; ++j) red2[wm * BN + col_of(j)] = make_float2(sj[j], mj[j]);
-    __syncthreads();
-    if (wm == 0 && lq == 0) {
-#pragma unroll
-      for (int j = 0; j < FN; ++j) {
-        const int c = col_of(j);
-        float2 t = red2[c];
-        float nt = (float)WM;
-#pragma unroll
-        for (int w = 1; w < WMW; ++w) {
-          const float2 u = red2[w * BN + c];
-          const float d = u.x / (float)WM - t.x / nt;
-          t.y = t.y + u.y + d * d * (nt * (float)WM / (nt + (float)WM));
-          t.x += u.x;
-          nt += (float)WM;
-        }
-        *(float2*)(a.stats + 2 * ((size_t)pt * a.Co + n0 + c)) = t;
-      }
-    }
-    __syncthreads();
-  }
-  float* stage = (float*)smem;
-  E* Y = (E*)a.y;
-  const E* R1 = (const E*)a.r;
-  const E* R2 = (const E*)a.r2;
-  const int s_rl = tid >> 3, s_cc = tid & 7;
-#pragma unroll
-  for (int pass = 0; pass < BN / EPI_COLS; ++pass) {
-    const int cbase = pass * EPI_COLS;
-    if (wn * WN + WN > cbase && wn * WN < cbase + EPI_COLS) {
-#pragma unroll
-      for (int j = 0; j < FN; ++j) {
-        const int col = col_of(j);
-        if (col >= cbase && col < cbase + EPI_COLS) {
-#pragma unroll
-          for (int i = 0; i < FM; ++i)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) stage[row_of(i, k) * EPI_LD + (col - cbase)] = acc[i][j][k];
-        }
-      }
-    }
-    __syncthreads();
-    const int n = n0 + cbase + s_cc * 8;
-    {
-#pragma unroll
-      for (int rr = 0; rr < BM / 64; ++rr) {
-        const int row = s_rl + 64 * rr;
-        const int ty = row / PT_W, tx = row - ty * PT_W;
-        const long m = ((long)nimg * a.Ho + ty0 + ty) * a.Wo + tx0 + tx;
-        const float* sp = stage + row * EPI_LD + s_cc * 8;
-        const float4 v0 = *(const float4*)sp, v1 = *(const float4*)(sp + 4);
-        float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-        if (R1) {
-          float u[8];
-          Vec8<E>::load(R1 + (size_t)m * a.ldr + n, u);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] += u[e];
-        }
-        if (R2) {
-          float u[8];
-          Vec8<E>::load(R2 + (size_t)m * a.ldr2 + n, u);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] += u[e];
-        }
-        store8_nt(Y + (size_t)m * a.ldy + n, v);
-      }
-    }
-    __syncthreads();
-  }
+  const AccLane<WM, WN> L{wave / WNW, wave % WNW, lane & 15, lane >> 4};
+  // no Co guards: Co % BN == 0 on the patch paths
+  if (a.stats) tile_stats_full<BN, WMW, false>(a, acc, smem, L, pt, n0);
+  tile_store_staged<E, BM, BN, false>(a, acc, smem, L, n0, [&](int row, long& m) {
+    const int ty = row / PT_W, tx = row - ty * PT_W;
+    m = ((long)nimg * a.Ho + ty0 + ty) * a.Wo + tx0 + tx;
+    return true;
+  });
 }
 
 template <typename E, int BN, int WMW, int WNW, int NPB, int NST, int OCC>
@@ -628,10 +369,7 @@ __global__ __launch_bounds__(V2_THREADS, 2 * OCC) void conv_nt_patch_kernel(Conv
   const int lr = lane & 15, lq = lane >> 4;
   const int tiles_x = a.Wo / PT_W, tiles_y = a.Ho / PT_H;
   const int ntiles = a.Co / BN;   // output-channel tiles (n fastest: they share the patch in L2)
-  const int nwg = a.N * tiles_y * tiles_x * ntiles;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int wg = xcd_tile(blockIdx.x, a.N * tiles_y * tiles_x * ntiles);
   const int n0 = (wg % ntiles) * BN;
   const int pt = wg / ntiles;     // pixel tile = BN-statistics partial index
   const int tx0 = (pt % tiles_x) * PT_W;
@@ -728,7 +466,7 @@ __global__ __launch_bounds__(V2_THREADS, 2 * OCC) void conv_nt_patch_kernel(Conv
       __builtin_amdgcn_s_setprio(0);
     }
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt<0>();
   __builtin_amdgcn_s_barrier();
 
   patch_epilogue<E, BN, WMW, WNW>(a, acc, smem, pt, n0, nimg, ty0, tx0);
@@ -758,10 +496,7 @@ __global__ __launch_bounds__(V2_THREADS, 4) void conv_nt_patch_s2d_kernel(ConvAr
   const int wm = wave;
   const int lr = lane & 15, lq = lane >> 4;
   const int tiles_x = a.Wo / PT_W, tiles_y = a.Ho / PT_H;
-  const int nwg = a.N * tiles_y * tiles_x;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int pt = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int pt = xcd_tile(blockIdx.x, a.N * tiles_y * tiles_x);
   const int tx0 = (pt % tiles_x) * PT_W;
   const int ty0 = ((pt / tiles_x) % tiles_y) * PT_H;
   const int nimg = pt / (tiles_x * tiles_y);
@@ -788,7 +523,7 @@ __global__ __launch_bounds__(V2_THREADS, 4) void conv_nt_patch_s2d_kernel(ConvAr
   for (int i = 0; i < FM; ++i)
 #pragma unroll
     for (int j = 0; j < FN; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt<0>();
   __builtin_amdgcn_s_barrier();
 #pragma unroll
   for (int kb = 0; kb < 4; ++kb) {
@@ -826,32 +561,17 @@ hipError_t patch_launch(const ConvArgs& a, hipStream_t s) {
   constexpr int LDS = NPB * PP_BYTES + NST * BN * 128;
   static_assert(LDS * OCC <= 160 * 1024 && LDS >= 256 * (64 + 4) * 4, "LDS budget / epilogue staging");
   static_assert(LDS == CONV_NT_PATCH_LDS, "the plan's LDS (conv_select.h)");
-  auto kern = conv_nt_patch_kernel<E, BN, WMW, WNW, NPB, NST, OCC>;
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) return e;
-    attr = true;
-  }
   const int nwg = a.N * (a.Ho / PT_H) * (a.Wo / PT_W) * (a.Co / BN);
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(V2_THREADS), LDS, s, a);
-  return hipGetLastError();
+  return launch_lds<conv_nt_patch_kernel<E, BN, WMW, WNW, NPB, NST, OCC>>(dim3(nwg), dim3(V2_THREADS), LDS, s, a);
 }
 
 template <typename E>
 hipError_t patch_s2d_launch(const ConvArgs& a, hipStream_t s) {
-  constexpr int LDS = 256 * (64 + 4) * 4;   // the epilogue staging (> 16 KB patch + 32 KB weights)
+  constexpr int LDS = 256 * EPI_LD * 4;   // the epilogue staging (> 16 KB patch + 32 KB weights)
   static_assert(PS_PIX * 32 + 4 * 8192 <= LDS, "LDS");
   static_assert(LDS == CONV_NT_PATCH_S2D_LDS, "the plan's LDS (conv_select.h)");
-  auto kern = conv_nt_patch_s2d_kernel<E>;
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) return e;
-    attr = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(a.N * (a.Ho / PT_H) * (a.Wo / PT_W)), dim3(V2_THREADS), LDS, s, a);
-  return hipGetLastError();
+  const int nwg = a.N * (a.Ho / PT_H) * (a.Wo / PT_W);
+  return launch_lds<conv_nt_patch_s2d_kernel<E>>(dim3(nwg), dim3(V2_THREADS), LDS, s, a);
 }
 
 // the instantiation a plan names (conv_select.cpp picks it; nothing is decided here)
@@ -859,8 +579,8 @@ template <typename E, int ST>
 hipError_t nt_tile_st(const ConvNtPlan& p, const ConvArgs& a, hipStream_t s) {
   if constexpr (ST == 1) {
     if (p.kernel == NT_V2_DUAL) {
-      if (p.bn == 128) return v2_launch<E, 128, 4, 2, 3, 1, 0, 16, 256, 1>(a, s);
-      return v2_launch<E, 64, 8, 1, 3, 1, 0, 16, 128, 1>(a, s);
+      if (p.bn == 128) return v2_launch<E, 128, 4, 2, 3, 1, 0, 256, 1>(a, s);
+      return v2_launch<E, 64, 8, 1, 3, 1, 0, 128, 1>(a, s);
     }
     if (p.kernel == NT_PATCH) return patch_launch<E, 64, 8, 1, 1, 3, 2>(a, s);
   }
@@ -869,7 +589,7 @@ hipError_t nt_tile_st(const ConvNtPlan& p, const ConvArgs& a, hipStream_t s) {
     case 256: return v2_launch<E, 256, 4, 2, 2, ST>(a, s);
     case 128: return v2_launch<E, 128, 4, 2, 3, ST>(a, s);
     case 64:
-      if (p.small) return v2_launch<E, 64, 8, 1, 3, ST, 0, 16, 128>(a, s);
+      if (p.small) return v2_launch<E, 64, 8, 1, 3, ST, 0, 128>(a, s);
       return v2_launch<E, 64, 8, 1, 3, ST>(a, s);
   }
   return hipErrorInvalidValue;
@@ -879,7 +599,7 @@ template <typename E>
 hipError_t nt_tile_e(const ConvNtPlan& p, const ConvArgs& a, hipStream_t s) {
   if (p.tap8) {   // the space-to-depth stem
     if (p.kernel == NT_PATCH_S2D) return patch_s2d_launch<E>(a, s);
-    if (p.small) return v2_launch<E, 64, 8, 1, 3, 1, 2, 16, 128>(a, s);
+    if (p.small) return v2_launch<E, 64, 8, 1, 3, 1, 2, 128>(a, s);
     return v2_launch<E, 64, 8, 1, 3, 1, 2>(a, s);
   }
   if (p.st == 1) return nt_tile_st<E, 1>(p, a, s);
@@ -937,14 +657,10 @@ __global__ __launch_bounds__(WG_THREADS, 1) void conv_wgrad_v2_kernel(WgradArgs 
   const int wm = wave / WNW, wn = wave % WNW;
   const int Ncol = a.KH * a.KW * a.C;
   const int P = a.N * a.Ho * a.Wo;
-  // XCD-aware bijective remap of the 1-D grid: workgroups are dealt round-robin over the 8
-  // XCDs; give each XCD a contiguous run of (split-major, co fastest) tiles so all tiles of a
-  // pixel split share one L2 (dy rows reused across column tiles, x rows across co tiles)
+  // tiles split-major, co fastest: all tiles of a pixel split share one XCD's L2 (dy rows
+  // reused across column tiles, x rows across co tiles)
   const int mtn = (a.Co + BM - 1) / BM, ntn = (Ncol + BN - 1) / BN;
-  const int nwg = mtn * ntn * a.splits;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int wg = xcd_tile(blockIdx.x, mtn * ntn * a.splits);
   const int split = wg / (mtn * ntn);
   const int rem = wg - split * mtn * ntn;
   const int nt_ = rem / mtn, mt_ = rem - nt_ * mtn;
@@ -1097,7 +813,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void conv_wgrad_v2_kernel(WgradArgs 
     if (kb + STAGES - 1 < nk) issue(kb + STAGES - 1, (kb + STAGES - 1) % STAGES);
     compute(kb % STAGES);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt<0>();
 
   float* O = a.out + (size_t)split * a.Co * Ncol;
   const int lr = lane & 15;
@@ -1136,17 +852,9 @@ hipError_t wg2_launch(const WgradArgs& a, hipStream_t s) {
   static_assert(LDS <= 160 * 1024, "LDS budget");
   static_assert(STAGES <= 4 && (STAGES < 4 || 2 * (WBK * (BM + BN) / 8 / WG_THREADS) <= 16), "vmcnt");
   static_assert(LDS == conv_wgrad_v2_lds(BM, BN), "the plan's LDS (conv_select.h)");
-  auto kern = conv_wgrad_v2_kernel<E, BM, BN, WMW, WNW, STAGES, WBK>;
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) return e;
-    attr = true;
-  }
   const int Ncol = a.KH * a.KW * a.C;
   const int nwg = ceil_div(a.Co, BM) * ceil_div(Ncol, BN) * a.splits;
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(WG_THREADS), LDS, s, a);
-  return hipGetLastError();
+  return launch_lds<conv_wgrad_v2_kernel<E, BM, BN, WMW, WNW, STAGES, WBK>>(dim3(nwg), dim3(WG_THREADS), LDS, s, a);
 }
 
 // the v2 tile a plan names (bm, bn in {64, 128, 256})

@@ -24,6 +24,7 @@
 //    layout of the other weight-gradient kernels).
 #include "conv.h"
 #include "conv_launch.h"
+#include "conv_tile.h"
 
 namespace {
 
@@ -172,8 +173,8 @@ __global__ __launch_bounds__(WP_THREADS, 1) void conv_wgrad_patch_kernel(WgradAr
     if (nk > 1) issue(t_begin + 1, 1);
     for (long k = 0; k < nk; ++k) {
       // stage k landed: only stage k+1's five pieces (if issued) may stay in flight
-      if (k + 1 < nk) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (k + 1 < nk) wait_vmcnt<5>();
+      else wait_vmcnt<0>();
       asm volatile("" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();   // every wave's pieces of stage k landed; stage k-1 read
@@ -219,13 +220,7 @@ __global__ __launch_bounds__(WP_THREADS, 1) void conv_wgrad_patch_kernel(WgradAr
 hipError_t launch_conv_wgrad_patch(int dtype, const ConvWgradPlan& p, const WgradArgs& a, hipStream_t s) {
   static_assert(WP_LDS == CONV_WGRAD_PATCH_LDS, "the plan's LDS (conv_select.h)");
   if (p.kernel != WG_PATCH || a.splits < 1) return hipErrorInvalidValue;
-  const int grid = (a.Co / 64) * (a.C / 64) * a.splits;
-  auto launch = [&](auto kern) -> hipError_t {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, WP_LDS);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WP_THREADS), WP_LDS, s, a);
-    return hipGetLastError();
-  };
-  if (dtype == SEG_F16) return launch(conv_wgrad_patch_kernel<f16_t>);
-  return launch(conv_wgrad_patch_kernel<bf16_t>);
+  const dim3 grid((a.Co / 64) * (a.C / 64) * a.splits), block(WP_THREADS);
+  if (dtype == SEG_F16) return launch_lds<conv_wgrad_patch_kernel<f16_t>>(grid, block, WP_LDS, s, a);
+  return launch_lds<conv_wgrad_patch_kernel<bf16_t>>(grid, block, WP_LDS, s, a);
 }
