@@ -434,6 +434,65 @@ int seg_op_conv_wgrad_plan(int dtype, const int* f, int nf, int flags, int force
 int seg_op_bootstrap_threshold(const float* map, int64_t n, int64_t k, float* tau_out,
                                int64_t* n_ge_out, void* stream);
 
+/* single batch-norm launches, as the network issues them (csrc/bn.h). Every buffer is
+ * a caller-owned device buffer, per-channel vectors are [C] floats, rows are pixels (ld = pixel
+ * stride in elements). dtype = SEG_DTYPE_* of y and of the 16-bit outputs. -EINVAL with a
+ * seg_last_error text, and no launch, for a bad argument and for every combination the
+ * launchers refuse. */
+/* the row blocks of the backward reduce for M rows: the caller sizes seg_bn_bwd_args.part as
+ * [rb][C][2] floats and cs_part as [rb][C] */
+int seg_op_bn_rowblocks(int64_t M, int C);
+/* forward statistics from the conv epilogue's per-tile partials part [ceil(M / tile_rows)][C][2]
+ * = (sum, M2 about the tile mean) of tile_rows rows each (the last tile ragged): mean, invstd =
+ * rsqrt(var + eps), scale = gamma invstd, var_unb = var N / (N - 1), and pack [2C] = [mean |
+ * E[x^2]] when not NULL */
+int seg_op_bn_stats_finalize(const float* part, int64_t M, int C, int tile_rows, const float* gamma,
+                             float* mean, float* invstd, float* scale, float* var_unb, float* pack,
+                             void* stream);
+/* out = act((y - mean) scale + beta [+ res | + (y2 - mean2) scale2 + beta2]); res subsampled by rs
+ * over an [N][Hr][Wr] grid when rs > 1 (the output grid is [N][Ho][Wo]); mask (nullable, with
+ * relu, 8-wide layouts only): bits [M][C/8] of out > 0 as stored */
+typedef struct seg_bn_apply_args {
+  const void* y; int ldy;
+  int64_t M; int C;
+  const float* mean; const float* scale; const float* beta;
+  int relu;
+  const void* res; int ldres; int rs; int Ho, Wo, Hr, Wr;
+  const void* y2; int ldy2; const float* mean2; const float* scale2; const float* beta2;
+  void* out; int ldo;
+  uint8_t* mask;
+} seg_bn_apply_args;
+int seg_op_bn_apply(int dtype, int out_f32, const seg_bn_apply_args* a, void* stream);
+/* one layer's backward: reduce into part, finalize (dgamma, dbeta nullable; sdy = dbeta / M,
+ * sdyx = dgamma / M, both 0 when frozen), then, unless reduce_only, the apply
+ * dy = scale (dyhat - sdy - xhat sdyx), where dyhat = gate(dz + dshift) dzscale. The gate is z > 0
+ * or the bits in mask, not both; with the bits, dzscale reaches the apply only (group norm's
+ * gamma: the sums are those of the gated dz). dyhat (nullable) receives the gated gradient before dzscale,
+ * from the apply, or from the reduce when reduce_only. cs_part with beta (16-bit, with dshift):
+ * per row block column sums of the forward output relu((y - mean) scale + beta) as stored. */
+typedef struct seg_bn_bwd_args {
+  const void* dz; int lddz;          /* dtype, or float when dz_f32 */
+  const void* z; int ldz;            /* the type of dz */
+  const uint8_t* mask;
+  const void* y; int ldy;
+  int64_t M; int C;
+  const float* mean; const float* invstd; const float* scale;
+  float* sdy; float* sdyx;
+  void* dy; int lddy;
+  void* dyhat; int lddyhat;
+  const float* dzscale; const float* dshift;
+  const float* beta; float* cs_part;
+  float* part;
+  float* dgamma; float* dbeta;
+} seg_bn_bwd_args;
+int seg_op_bn_backward(int dtype, int dz_f32, int frozen, int reduce_only, const seg_bn_bwd_args* a,
+                       void* stream);
+/* two layers gated by the same dz and bits (a->dz, a->mask): one dual reduce, a finalize each,
+ * one dual apply; b supplies the second layer's y, statistics, outputs and partials (same M, C).
+ * second_only: dz arrived gated, and only the second layer's apply runs, ungated. */
+int seg_op_bn_backward_dual(int dtype, int frozen, int second_only, const seg_bn_bwd_args* a,
+                            const seg_bn_bwd_args* b, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,35 @@ void op_geom(int H, int W, int k, int stride, int rate, int explicit_pad, int* H
   *Ho = L.Ho; *Wo = L.Wo; *ph = L.pad_h; *pw = L.pad_w;
 }
 
+bool bad_dtype(int dtype) {
+  return dtype != SEG_DTYPE_F32 && dtype != SEG_DTYPE_BF16 && dtype != SEG_DTYPE_F16;
+}
+
+// the pointers and strides every BN-backward entry needs (dy only where an apply runs)
+int bn_bwd_check(const char* who, int dtype, const seg_bn_bwd_args* p, bool need_dy) {
+  if (!p || bad_dtype(dtype) || !p->dz || !p->y || !p->mean || !p->invstd || !p->scale || !p->sdy ||
+      !p->sdyx || !p->part || p->M < 1 || p->C < 1 || p->lddz < p->C || p->ldy < p->C ||
+      (need_dy && (!p->dy || p->lddy < p->C)))
+    return set_err(nullptr, -EINVAL, "%s: bad arguments", who);
+  return 0;
+}
+
+// the network's bn_bwd_args (net_layers.cpp) from the C struct; rb as the network sizes it
+BnBwdArgs bn_bwd_op_args(const seg_bn_bwd_args* p) {
+  BnBwdArgs a{};
+  a.dz = p->dz; a.lddz = p->lddz;
+  a.z = p->z; a.ldz = p->ldz; a.mask = p->mask;
+  a.y = p->y; a.ldy = p->ldy; a.M = (long)p->M; a.C = p->C;
+  a.mean = p->mean; a.invstd = p->invstd; a.scale = p->scale;
+  a.sdy = p->sdy; a.sdyx = p->sdyx;
+  a.dy = p->dy; a.lddy = p->lddy;
+  a.dyhat = p->dyhat; a.lddyhat = p->lddyhat;
+  a.dzscale = p->dzscale; a.dshift = p->dshift;
+  a.beta = p->beta; a.cs_part = p->cs_part;
+  a.part = p->part; a.rb = bn_bwd_rowblocks(a.M, a.C);
+  return a;
+}
+
 // ---- checkpoint interop: CRC-32C (Castagnoli) of host bytes, the checksum TF 1.12 tensor
 // bundles store per tensor and per table block (tensorflow/core/lib/hash/crc32c.h), used by
 // utils/tf_checkpoint.py to read / write <prefix>.index + <prefix>.data-* checkpoints
@@ -320,6 +349,107 @@ int seg_op_conv_wgrad_cfg(int dtype, const void* dy, int N, int Ho, int Wo, int 
   hipError_t e = launch_conv_wgrad(dt_of(dtype), a, s, bm, bn);
   if (e == hipSuccess) e = launch_splitk_reduce((float*)workspace, splits, n, n, dw, 0, s);
   return e == hipSuccess ? 0 : hip_fail(nullptr, e, "seg_op_conv_wgrad_cfg");
+}
+
+int seg_op_bn_rowblocks(int64_t M, int C) {
+  if (M < 1 || C < 1) return set_err(nullptr, -EINVAL, "seg_op_bn_rowblocks: bad arguments");
+  return bn_bwd_rowblocks((long)M, C);
+}
+
+int seg_op_bn_stats_finalize(const float* part, int64_t M, int C, int tile_rows, const float* gamma,
+                             float* mean, float* invstd, float* scale, float* var_unb, float* pack,
+                             void* stream) {
+  if (!part || !gamma || !mean || !invstd || !scale || !var_unb || M < 1 || C < 1 || tile_rows < 1)
+    return set_err(nullptr, -EINVAL, "seg_op_bn_stats_finalize: bad arguments");
+  BnState st{};
+  st.mean = mean; st.invstd = invstd; st.scale = scale; st.var_unb = var_unb;
+  hipError_t e = launch_bn_stats_finalize(part, (long)M, C, tile_rows, nullptr, gamma, st,
+                                          (hipStream_t)stream, pack);
+  return e == hipSuccess ? 0 : hip_fail(nullptr, e, "seg_op_bn_stats_finalize");
+}
+
+int seg_op_bn_apply(int dtype, int out_f32, const seg_bn_apply_args* p, void* stream) {
+  if (!p || bad_dtype(dtype) || !p->y || !p->out || !p->mean || !p->scale || !p->beta || p->M < 1 ||
+      p->C < 1 || p->ldy < p->C || p->ldo < p->C)
+    return set_err(nullptr, -EINVAL, "seg_op_bn_apply: bad arguments");
+  if (dtype == SEG_DTYPE_F32 && !out_f32)
+    return set_err(nullptr, -EINVAL, "seg_op_bn_apply: a 32-bit input has a 32-bit output");
+  if (p->y2 && (p->res || !p->mean2 || !p->scale2 || !p->beta2 || p->ldy2 < p->C))
+    return set_err(nullptr, -EINVAL, "seg_op_bn_apply: the second BN takes the place of the residual "
+                   "and needs its own mean2 / scale2 / beta2");
+  if (p->res && (p->ldres < p->C || p->rs < 1 ||
+                 (p->rs > 1 && (p->Ho < 1 || p->Wo < 1 || p->M % ((int64_t)p->Ho * p->Wo) ||
+                                (p->Ho - 1) * p->rs >= p->Hr || (p->Wo - 1) * p->rs >= p->Wr))))
+    return set_err(nullptr, -EINVAL, "seg_op_bn_apply: the subsampled residual grid does not cover "
+                   "the output grid");
+  BnApplyArgs a{};
+  a.y = p->y; a.ldy = p->ldy; a.M = (long)p->M; a.C = p->C;
+  a.mean = p->mean; a.scale = p->scale; a.beta = p->beta; a.relu = p->relu;
+  a.res = p->res; a.ldres = p->ldres; a.rs = p->rs;
+  a.Ho = p->Ho; a.Wo = p->Wo; a.Hr = p->Hr; a.Wr = p->Wr;
+  a.y2 = p->y2; a.ldy2 = p->ldy2; a.mean2 = p->mean2; a.scale2 = p->scale2; a.beta2 = p->beta2;
+  a.out = p->out; a.ldo = p->ldo; a.mask = p->mask;
+  if (a.mask && (!a.relu || !bn_apply_is_v8(a)))
+    return set_err(nullptr, -EINVAL, "seg_op_bn_apply: ReLU bits exist on the 8-wide path only, "
+                   "with relu");
+  hipError_t e = launch_bn_apply(dt_of(dtype), out_f32, a, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : hip_fail(nullptr, e, "seg_op_bn_apply");
+}
+
+int seg_op_bn_backward(int dtype, int dz_f32, int frozen, int reduce_only, const seg_bn_bwd_args* p,
+                       void* stream) {
+  const char* who = "seg_op_bn_backward";
+  if (int r = bn_bwd_check(who, dtype, p, !reduce_only)) return r;
+  if (dtype == SEG_DTYPE_F32) dz_f32 = 0;   // dz is of the storage type
+  if (p->z && p->mask) return set_err(nullptr, -EINVAL, "%s: the gate is z or the bits, not both", who);
+  if (p->z && p->ldz < p->C) return set_err(nullptr, -EINVAL, "%s: bad arguments", who);
+  if (p->dyhat && p->lddyhat < p->C) return set_err(nullptr, -EINVAL, "%s: bad arguments", who);
+  BnBwdArgs a = bn_bwd_op_args(p);
+  a.reduce_dyhat = reduce_only && p->dyhat ? 1 : 0;
+  const char* why = bn_bwd_reduce_refusal(dt_of(dtype), a);
+  if (!why && !reduce_only) why = bn_bwd_apply_refusal(a);
+  if (why) return set_err(nullptr, -EINVAL, "%s: %s", who, why);
+  hipStream_t s = (hipStream_t)stream;
+  BnState st{};
+  st.sdy = p->sdy; st.sdyx = p->sdyx;
+  hipError_t e = launch_bn_bwd_reduce(dt_of(dtype), dz_f32, a, s);
+  if (e == hipSuccess) e = launch_bn_bwd_finalize(a.part, a.rb, a.M, a.C, st, p->dgamma, p->dbeta, s, frozen);
+  if (e == hipSuccess && !reduce_only) e = launch_bn_bwd_apply(dt_of(dtype), dz_f32, a, s);
+  return e == hipSuccess ? 0 : hip_fail(nullptr, e, who);
+}
+
+int seg_op_bn_backward_dual(int dtype, int frozen, int second_only, const seg_bn_bwd_args* p,
+                            const seg_bn_bwd_args* q, void* stream) {
+  const char* who = "seg_op_bn_backward_dual";
+  if (int r = bn_bwd_check(who, dtype, p, !second_only)) return r;
+  if (int r = bn_bwd_check(who, dtype, q, true)) return r;
+  if (q->M != p->M || q->C != p->C || !p->mask || q->part == p->part || p->dshift || p->cs_part)
+    return set_err(nullptr, -EINVAL, "%s: two layers of one shape with partials of their own, gated "
+                   "by the first's bits", who);
+  BnBwdArgs a = bn_bwd_op_args(p);
+  seg_bn_bwd_args alone = *q;   // the second layer alone: ungated, dz of the storage type
+  alone.dz = p->dz; alone.lddz = p->lddz;
+  alone.z = nullptr; alone.mask = nullptr; alone.dyhat = nullptr;
+  alone.dzscale = nullptr; alone.dshift = nullptr; alone.cs_part = nullptr;
+  const BnBwdArgs a2 = bn_bwd_op_args(&alone);
+  a.y2 = a2.y; a.ldy2 = a2.ldy;
+  a.mean2 = a2.mean; a.invstd2 = a2.invstd; a.scale2 = a2.scale;
+  a.sdy2 = a2.sdy; a.sdyx2 = a2.sdyx;
+  a.dy2 = a2.dy; a.lddy2 = a2.lddy;
+  a.part2 = a2.part;
+  hipStream_t s = (hipStream_t)stream;
+  BnState st{}, st2{};
+  st.sdy = p->sdy; st.sdyx = p->sdyx;
+  st2.sdy = q->sdy; st2.sdyx = q->sdyx;
+  hipError_t e = launch_bn_bwd_reduce_dual(dt_of(dtype), a, s);
+  if (e == hipErrorInvalidValue)
+    return set_err(nullptr, -EINVAL, "%s: the dual kernels take 8-wide layouts, the bits, and no z / "
+                   "dzscale / dyhat", who);
+  if (e == hipSuccess) e = launch_bn_bwd_finalize(a.part, a.rb, a.M, a.C, st, p->dgamma, p->dbeta, s, frozen);
+  if (e == hipSuccess) e = launch_bn_bwd_finalize(a2.part, a2.rb, a.M, a.C, st2, q->dgamma, q->dbeta, s, frozen);
+  if (e == hipSuccess)
+    e = second_only ? launch_bn_bwd_apply(dt_of(dtype), 0, a2, s) : launch_bn_bwd_apply_dual(dt_of(dtype), a, s);
+  return e == hipSuccess ? 0 : hip_fail(nullptr, e, who);
 }
 
 uint32_t seg_crc32c(uint32_t crc, const void* data, size_t n) {

@@ -77,7 +77,13 @@ hipError_t launch_bn_infer_finalize_all(const BnInferJob* jobs, int n, hipStream
 hipError_t launch_bn_infer_finalize(const float* mov_mean, const float* mov_var, int C,
                                     const float* gamma, BnState st, hipStream_t s);
 hipError_t launch_bn_apply(int dtype, int out_f32, const BnApplyArgs& a, hipStream_t s);
+// does this launch take the 8-channel streaming kernels (the only ones that write ReLU bits)?
+bool bn_apply_is_v8(const BnApplyArgs& a);
 int bn_bwd_rowblocks(long M, int C);
+// why launch_bn_bwd_reduce / launch_bn_bwd_apply return hipErrorInvalidValue for these arguments
+// without launching (nullptr: they launch); the launchers test exactly these
+const char* bn_bwd_reduce_refusal(int dtype, const BnBwdArgs& a);
+const char* bn_bwd_apply_refusal(const BnBwdArgs& a);
 hipError_t launch_bn_bwd_reduce(int dtype, int dz_f32, const BnBwdArgs& a, hipStream_t s);
 // frozen: is_training=False statistics (moving averages): the batch means do not depend on
 // the input, so sdy = sdyx = 0 and dy = gamma * invstd * dyhat (FusedBatchNormGrad, inference)

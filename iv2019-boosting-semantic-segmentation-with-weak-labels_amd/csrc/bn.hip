@@ -824,12 +824,15 @@ int grid_for(long items) {
   return (int)(g < 4096 ? (g < 1 ? 1 : g) : 4096);
 }
 
+bool apply_v8(const BnApplyArgs& a) {
+  return (a.C % 8 == 0) && (a.ldy % 8 == 0) && (a.ldo % 8 == 0) &&
+         (!a.res || a.ldres % 8 == 0) && (!a.y2 || a.ldy2 % 8 == 0) &&
+         (((uintptr_t)a.out) % 16 == 0);
+}
+
 template <typename T, typename TO>
 hipError_t apply_t(const BnApplyArgs& a, hipStream_t s) {
-  bool v8 = (a.C % 8 == 0) && (a.ldy % 8 == 0) && (a.ldo % 8 == 0) &&
-            (!a.res || a.ldres % 8 == 0) && (!a.y2 || a.ldy2 % 8 == 0) &&
-            (((uintptr_t)a.out) % 16 == 0);
-  if (v8) {
+  if (apply_v8(a)) {
     const int res = a.y2 ? RES_BN2 : (a.res ? (a.rs > 1 ? RES_SUB : RES_PLAIN) : RES_NONE);
     const dim3 g = grid8(a.M, a.C);
 #define BN_APPLY_CASE(R)                                                                      \
@@ -844,7 +847,6 @@ hipError_t apply_t(const BnApplyArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-template <typename T, typename TZ>
 bool bwd_v8(const BnBwdArgs& a) {
   return (a.C % 8 == 0) && (a.lddz % 8 == 0) && (a.ldy % 8 == 0) && (!a.z || a.ldz % 8 == 0) &&
          (!a.dy || a.lddy % 8 == 0) && (!a.dyhat || a.lddyhat % 8 == 0) &&
@@ -853,11 +855,9 @@ bool bwd_v8(const BnBwdArgs& a) {
 
 template <typename T, typename TZ>
 hipError_t bwd_reduce_t(const BnBwdArgs& a, hipStream_t s) {
-  if (a.mask && !bwd_v8<T, TZ>(a)) return hipErrorInvalidValue;   // bits exist on the 8-wide path only
+  if (bn_bwd_reduce_refusal(sizeof(T) == 2 ? SEG_BF16 : SEG_F32, a)) return hipErrorInvalidValue;
   const bool rdh = a.reduce_dyhat && a.dyhat;
-  if ((a.dshift || rdh) && (!a.mask || a.dzscale || !bwd_v8<T, TZ>(a))) return hipErrorInvalidValue;
-  if (a.cs_part && (!a.dshift || rdh || !a.beta || sizeof(T) != 2)) return hipErrorInvalidValue;
-  if (bwd_v8<T, TZ>(a)) {
+  if (bwd_v8(a)) {
     const int cg_n = a.C / 8;
     const dim3 g(a.rb, cg_n > 256 ? ceil_div(cg_n, 256) : 1);
     if (a.cs_part) hipLaunchKernelGGL((bn_bwd_reduce8_kernel<T, TZ, 2, 2, 0, 1>), g, dim3(256), 0, s, a);
@@ -876,9 +876,8 @@ hipError_t bwd_reduce_t(const BnBwdArgs& a, hipStream_t s) {
 
 template <typename T, typename TZ>
 hipError_t bwd_apply_t(const BnBwdArgs& a, hipStream_t s) {
-  if (a.mask && !bwd_v8<T, TZ>(a)) return hipErrorInvalidValue;
-  if (a.dshift && (!a.mask || a.dzscale || a.dyhat || !bwd_v8<T, TZ>(a))) return hipErrorInvalidValue;
-  if (bwd_v8<T, TZ>(a)) {
+  if (bn_bwd_apply_refusal(a)) return hipErrorInvalidValue;
+  if (bwd_v8(a)) {
     const dim3 g = grid8(a.M, a.C);
     const int key = (a.z ? 4 : 0) | (a.dzscale ? 2 : 0) | (a.dyhat ? 1 : 0);
     if (a.dshift) {
@@ -912,6 +911,25 @@ hipError_t bwd_apply_t(const BnBwdArgs& a, hipStream_t s) {
 }
 
 }  // namespace
+
+bool bn_apply_is_v8(const BnApplyArgs& a) { return apply_v8(a); }
+
+const char* bn_bwd_reduce_refusal(int dtype, const BnBwdArgs& a) {
+  if (a.mask && !bwd_v8(a)) return "ReLU bits exist on the 8-wide path only";
+  const bool rdh = a.reduce_dyhat && a.dyhat;
+  if ((a.dshift || rdh) && (!a.mask || a.dzscale || !bwd_v8(a)))
+    return "dshift / a reduce-side dyhat need the ReLU bits, the 8-wide path and no dzscale";
+  if (a.cs_part && (!a.dshift || rdh || !a.beta || !seg_half(dtype)))
+    return "cs_part needs dshift, beta, a 16-bit type and no reduce-side dyhat";
+  return nullptr;
+}
+
+const char* bn_bwd_apply_refusal(const BnBwdArgs& a) {
+  if (a.mask && !bwd_v8(a)) return "ReLU bits exist on the 8-wide path only";
+  if (a.dshift && (!a.mask || a.dzscale || a.dyhat || !bwd_v8(a)))
+    return "dshift in the apply needs the ReLU bits, the 8-wide path, no dzscale and no dyhat";
+  return nullptr;
+}
 
 hipError_t launch_bn_stats_finalize(const float* tile_part, long M, int C, int tile_rows,
                                     float* scratch, const float* gamma, BnState st,

@@ -26,7 +26,8 @@ EXPORTED_SYMBOLS = [
     "seg_profile_read", "seg_op_conv_fwd", "seg_op_conv_stat_rows", "seg_op_conv_dgrad",
     "seg_op_conv_dgrad_res",
     "seg_op_conv_wgrad", "seg_op_conv_wgrad_cfg", "seg_op_conv_dgrad_fused",
-    "seg_op_conv_plan", "seg_op_conv_wgrad_plan", "seg_bbox_labels", "seg_tag_labels",
+    "seg_op_conv_plan", "seg_op_conv_wgrad_plan", "seg_op_bn_rowblocks", "seg_op_bn_stats_finalize",
+    "seg_op_bn_apply", "seg_op_bn_backward", "seg_op_bn_backward_dual", "seg_bbox_labels", "seg_tag_labels",
     "seg_grad_buckets", "seg_stream_wait_bucket", "seg_set_loss_scale", "seg_found_inf",
     "seg_set_bn_sync", "seg_set_bn_inference", "seg_predict", "seg_full_predictions",
     "seg_set_nesterov", "seg_set_defer_stem", "seg_flush_grads", "seg_set_premask", "seg_set_lbf",
@@ -58,6 +59,33 @@ class SegCfg(ctypes.Structure):
         ("bn_decay", ctypes.c_float), ("train_bn", ctypes.c_int),
         ("weight_decay", ctypes.c_float), ("fov_k", ctypes.c_int), ("fov_rate", ctypes.c_int),
         ("upsampling", ctypes.c_int), ("norm", ctypes.c_int), ("groups", ctypes.c_int),
+    ]
+
+
+_VP, _FP, _INT = ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int
+
+
+class BnApplyArgs(ctypes.Structure):
+    """seg_bn_apply_args (include/seg_hip.h); pointers are device addresses (tensor.data_ptr())"""
+    _fields_ = [
+        ("y", _VP), ("ldy", _INT), ("M", ctypes.c_int64), ("C", _INT),
+        ("mean", _FP), ("scale", _FP), ("beta", _FP), ("relu", _INT),
+        ("res", _VP), ("ldres", _INT), ("rs", _INT),
+        ("Ho", _INT), ("Wo", _INT), ("Hr", _INT), ("Wr", _INT),
+        ("y2", _VP), ("ldy2", _INT), ("mean2", _FP), ("scale2", _FP), ("beta2", _FP),
+        ("out", _VP), ("ldo", _INT), ("mask", _VP),
+    ]
+
+
+class BnBwdArgs(ctypes.Structure):
+    """seg_bn_bwd_args (include/seg_hip.h)"""
+    _fields_ = [
+        ("dz", _VP), ("lddz", _INT), ("z", _VP), ("ldz", _INT), ("mask", _VP),
+        ("y", _VP), ("ldy", _INT), ("M", ctypes.c_int64), ("C", _INT),
+        ("mean", _FP), ("invstd", _FP), ("scale", _FP), ("sdy", _FP), ("sdyx", _FP),
+        ("dy", _VP), ("lddy", _INT), ("dyhat", _VP), ("lddyhat", _INT),
+        ("dzscale", _FP), ("dshift", _FP), ("beta", _FP), ("cs_part", _FP),
+        ("part", _FP), ("dgamma", _FP), ("dbeta", _FP),
     ]
 
 
@@ -113,6 +141,12 @@ def _load():
         "seg_op_conv_wgrad_plan": (ip, [ip, ctypes.POINTER(ctypes.c_int), ip, ip, ip, ip, ctypes.c_char_p, ip]),
         "seg_op_conv_dgrad_fused": (ip, [ip, vp, ip, ip, ip, ip, ip, vp, ip, ip, ip, vp, ip,
                                          vp, ip, vp, ip, vp, ip, ip, vp, vp, vp]),
+        "seg_op_bn_rowblocks": (ip, [i64, ip]),
+        "seg_op_bn_stats_finalize": (ip, [vp, i64, ip, ip, vp, vp, vp, vp, vp, vp, vp]),
+        "seg_op_bn_apply": (ip, [ip, ip, ctypes.POINTER(BnApplyArgs), vp]),
+        "seg_op_bn_backward": (ip, [ip, ip, ip, ip, ctypes.POINTER(BnBwdArgs), vp]),
+        "seg_op_bn_backward_dual": (ip, [ip, ip, ip, ctypes.POINTER(BnBwdArgs),
+                                         ctypes.POINTER(BnBwdArgs), vp]),
         "seg_bbox_labels": (ip, [vp, vp, vp, vp, ip, ip, ip, ip, vp, vp]),
         "seg_grad_buckets": (ip, [vp, ip, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
         "seg_stream_wait_bucket": (ip, [vp, ip, vp]),

@@ -388,3 +388,41 @@ def test_train_distribute_self_launch_propagates_failure(tmp_path):
                         "--distribute"], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode != 0
     assert "exited with" in r.stderr and "a rank failed" in r.stderr, r.stderr[-3000:]
+
+
+def test_bn_op_structs_match_header(tmp_path):
+    """seg_bn_apply_args / seg_bn_bwd_args in ctypes lay out as a C compiler lays out the header's"""
+    import ctypes
+    import subprocess
+    import seg_hip
+    pairs = [("seg_bn_apply_args", seg_hip.BnApplyArgs), ("seg_bn_bwd_args", seg_hip.BnBwdArgs)]
+    body = "".join(f'printf("%zu", sizeof({c}));' + "".join(
+        f'printf(" %zu", offsetof({c}, {f[0]}));' for f in s._fields_) + 'printf("\\n");' for c, s in pairs)
+    src = tmp_path / "layout.c"
+    src.write_text('#include "seg_hip.h"\n#include <stddef.h>\n#include <stdio.h>\n'
+                   f"int main(void) {{ {body} return 0; }}\n")
+    exe = tmp_path / "layout"
+    subprocess.run(["gcc", "-std=c99", "-I", os.path.dirname(HEADER), str(src), "-o", str(exe)], check=True)
+    lines = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines()
+    for (c, s), line in zip(pairs, lines):
+        want = [ctypes.sizeof(s)] + [getattr(s, f[0]).offset for f in s._fields_]
+        assert [int(v) for v in line.split()] == want, c
+
+
+def test_bn_op_entries_validate_before_any_launch():
+    """no GPU is touched: the row-block count, and -EINVAL with a text for null / bad arguments"""
+    import ctypes
+    import errno
+    import seg_hip
+    L = seg_hip.LIB
+    assert [L.seg_op_bn_rowblocks(m, 64) for m in (1, 64, 65, 391, 65536, 66000)] == [1, 1, 2, 7, 1024, 1024]
+    assert L.seg_op_bn_rowblocks(0, 64) == -errno.EINVAL
+    assert L.seg_op_bn_stats_finalize(None, 10, 8, 64, None, None, None, None, None, None, None) == -errno.EINVAL
+    assert b"seg_op_bn_stats_finalize" in L.seg_last_error(None)
+    assert L.seg_op_bn_apply(1, 0, None, None) == -errno.EINVAL
+    a = seg_hip.BnApplyArgs()
+    assert L.seg_op_bn_apply(1, 0, ctypes.byref(a), None) == -errno.EINVAL
+    b = seg_hip.BnBwdArgs()
+    assert L.seg_op_bn_backward(7, 0, 0, 0, ctypes.byref(b), None) == -errno.EINVAL
+    assert L.seg_op_bn_backward_dual(1, 0, 0, ctypes.byref(b), None, None) == -errno.EINVAL
+    assert b"seg_op_bn_backward_dual" in L.seg_last_error(None)
