@@ -207,6 +207,50 @@ int seg_predict(seg_ctx* ctx, const int32_t* cid_map, int n_map, int replace_voi
 int seg_full_predictions(seg_ctx* ctx, float* logits_out, float* probs_out,
                          int32_t* head_decisions_out, int32_t* decisions_out, void* stream);
 
+/* test-time augmentation: multi-scale and flip inference (no reference counterpart; the semantics
+ * are fixed here). The caller runs one moving-statistics forward per entry -- a scale s of the
+ * batch, mirrored in x or not -- in a context of that entry's size, and hands the entries'
+ * low-resolution logits (what seg_outputs returns as logits_lowres) to one decision launch.
+ * seg_resize_images: the image pyramid. in fp32 [n][H][W][3] -> out fp32 [n][h_out][w_out][3] by
+ *   TF 1.12's legacy bilinear resize with align_corners = False, the arithmetic of
+ *   seg_prepare_images: scale = (float)in / (float)out, in_f = o * scale, lo = (int)in_f,
+ *   hi = min(lo + 1, in - 1), top = tl + (tr - tl) * xl, bot likewise, v = top + (bot - top) * yl,
+ *   every operation rounded to fp32 on its own. flip = 1 reads source column W - 1 - x_src: the
+ *   mirror, then the resize. With equal sizes the lerp weights are exactly 0, so flip = 0 copies
+ *   and flip = 1 mirrors bit for bit (a -0.0f may come out as +0.0f). -EINVAL for a null
+ *   pointer with n > 0, n < 0, a size < 1 or flip outside 0..1.
+ * seg_tta_decisions: N, H, W (the network size) and the head tables come from ctx; the context's
+ *   own logits are not read. entries is a host array of n_entries records: logits device fp32
+ *   [N][h_low][w_low][ld] (channels l1 | l2 vehicle | l2 human, ld >= c1 + c2 + c3 the pixel
+ *   stride), flip = 1 when the entry saw the mirrored image. For network pixel (n, y, x) and
+ *   entry e: u_e = ResizeBilinear(align_corners = True) of the entry's logits to H x W at column
+ *   x, or W - 1 - x for a flipped entry; p_e = the per-head softmax of u_e (max-subtracted, fast
+ *   exp, one reciprocal), both exactly as seg_predict forms them; sum = p_1 + ... + p_E in entry
+ *   order in fp32, starting from p_1; mean = sum * (1.0f / E). Decisions: per-head first-maximum
+ *   argmax of the sums -> hierarchical fusion (hierarchical.py:113-117) -> cid_map as in
+ *   seg_predict (-1 -> max + 1) -> replace_voids = 1: the stable top-2 of the l1 sums, as mode 1
+ *   of seg_predict -> NEAREST_NEIGHBOR align_corners resize to out_h x out_w; only the network
+ *   pixels the output pixels select are computed, and no full-resolution tensor is written.
+ *   replace_voids = 2 (seg_predict's PREDICT order on resized probabilities) is not defined for
+ *   averaged probabilities: -EINVAL. decisions_out: device int32 [N][out_h][out_w].
+ *   mean_probs_out: optional (NULL skips it) device fp32 [N][H][W][c1 + c2 + c3], 16-byte
+ *   aligned; needs out_h x out_w = H x W.
+ *   With one unflipped entry holding the context's own logits, decisions_out is bitwise what
+ *   seg_predict writes in modes 0 and 1 and mean_probs_out is bitwise probs_out of
+ *   seg_full_predictions.
+ *   -EINVAL with a seg_last_error text, and no launch, for: n_entries outside
+ *   1..SEG_TTA_MAX_ENTRIES; a null ctx, entries, logits, cid_map or decisions_out; h_low or
+ *   w_low < 1; ld < c1 + c2 + c3; flip outside 0..1; replace_voids outside 0..1; a cid map of
+ *   the wrong length or with an entry < -1; an output size < 1; mean_probs_out misaligned or
+ *   given with an output size other than H x W. */
+#define SEG_TTA_MAX_ENTRIES 16
+typedef struct seg_tta_entry { const float* logits; int h_low, w_low, ld, flip; } seg_tta_entry;
+int seg_resize_images(const float* in, int n, int H, int W, int h_out, int w_out, int flip,
+                      float* out, void* stream);
+int seg_tta_decisions(seg_ctx* ctx, const seg_tta_entry* entries, int n_entries,
+                      const int32_t* cid_map, int n_map, int replace_voids, int out_h, int out_w,
+                      float* mean_probs_out, int32_t* decisions_out, void* stream);
+
 /* input preprocessing (input_cityscapes.py:66-96,190-209), after the host
  * decodes TFRecord -> tf.train.Example -> PNG (input_pipelines/tfrecords.py):
  * seg_prepare_images: raw uint8 [n][src_h][src_w][3] -> convert_image_dtype -> bilinear

@@ -216,6 +216,61 @@ int seg_full_predictions(seg_ctx* c, float* logits_out, float* probs_out,
   return 0;
 }
 
+int seg_tta_decisions(seg_ctx* c, const seg_tta_entry* entries, int n_entries,
+                      const int32_t* cid_map, int n_map, int replace_voids, int out_h, int out_w,
+                      float* mean_probs_out, int32_t* decisions_out, void* stream) {
+  const char* who = "seg_tta_decisions";
+  if (!c) return set_err(nullptr, -EINVAL, "%s: null ctx", who);
+  if (!entries || !cid_map || !decisions_out)
+    return set_err(&c->err, -EINVAL, "%s: null entries / cid_map / decisions_out", who);
+  if (n_entries < 1 || n_entries > SEG_TTA_MAX_ENTRIES)
+    return set_err(&c->err, -EINVAL, "%s: %d entries (1..%d)", who, n_entries, SEG_TTA_MAX_ENTRIES);
+  static_assert(SEG_TTA_MAX_ENTRIES == TTA_MAX_ENTRIES, "entry table size");
+  const seg_cfg& g = c->cfg;
+  const LossTables& t = c->tables;
+  const int ct = t.c1 + t.c2 + t.c3;
+  if (replace_voids == 2)
+    return set_err(&c->err, -EINVAL, "%s: replace_voids = 2 (the PREDICT order on resized "
+                   "probabilities) is not defined for averaged probabilities; use 1", who);
+  if (replace_voids < 0 || replace_voids > 1)
+    return set_err(&c->err, -EINVAL, "%s: replace_voids = %d (0 or 1)", who, replace_voids);
+  if (n_map != t.n_pp)
+    return set_err(&c->err, -EINVAL, "%s: cid map has %d entries, the model has %d training classes",
+                   who, n_map, t.n_pp);
+  if (out_h < 1 || out_w < 1)
+    return set_err(&c->err, -EINVAL, "%s: bad output size %dx%d", who, out_h, out_w);
+  if (mean_probs_out && (reinterpret_cast<uintptr_t>(mean_probs_out) & 15))
+    return set_err(&c->err, -EINVAL, "%s: mean_probs_out must be 16-byte aligned", who);
+  if (mean_probs_out && (out_h != g.height || out_w != g.width))
+    return set_err(&c->err, -EINVAL, "%s: mean_probs_out needs the output size %dx%d to be the "
+                   "network size %dx%d", who, out_h, out_w, g.height, g.width);
+  TtaArgs a{};
+  for (int i = 0; i < n_entries; ++i) {
+    const seg_tta_entry& e = entries[i];
+    if (!e.logits) return set_err(&c->err, -EINVAL, "%s: entry %d: null logits", who, i);
+    if (e.h_low < 1 || e.w_low < 1)
+      return set_err(&c->err, -EINVAL, "%s: entry %d: low-resolution size %dx%d", who, i, e.h_low, e.w_low);
+    if (e.ld < ct)
+      return set_err(&c->err, -EINVAL, "%s: entry %d: pixel stride %d < %d channels", who, i, e.ld, ct);
+    if (e.flip < 0 || e.flip > 1)
+      return set_err(&c->err, -EINVAL, "%s: entry %d: flip = %d (0 or 1)", who, i, e.flip);
+    a.e[i] = TtaEntry{e.logits, e.h_low, e.w_low, e.ld, e.flip};
+  }
+  a.n_entries = n_entries;
+  a.inv_e = 1.0f / (float)n_entries;
+  a.N = c->logits.N; a.H = g.height; a.W = g.width; a.Ho = out_h; a.Wo = out_w;
+  a.replace_voids = replace_voids; a.n_map = n_map;
+  a.probs = mean_probs_out; a.out = decisions_out;
+  int mx = -1;
+  for (int i = 0; i < n_map; ++i) mx = std::max(mx, (int)cid_map[i]);
+  for (int i = 0; i < n_map; ++i) {   // utils._replacevoids: -1 -> max + 1
+    if (cid_map[i] < -1) return set_err(&c->err, -EINVAL, "%s: cid_map[%d] = %d", who, i, cid_map[i]);
+    a.map[i] = cid_map[i] == -1 ? mx + 1 : cid_map[i];
+  }
+  HIPCALL(c, launch_tta_decisions(a, t, (hipStream_t)stream));
+  return 0;
+}
+
 int seg_backward(seg_ctx* c, void* stream) {
   NEED_BOUND(c);
   Step S{c, (hipStream_t)stream, c->dt};

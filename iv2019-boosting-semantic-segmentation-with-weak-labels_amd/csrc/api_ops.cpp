@@ -1,5 +1,6 @@
 // The context-free entries of the C ABI (include/seg_hip.h): single conv launches for tests and
-// tools, label / input / augmentation preparation, the bootstrap threshold and the checkpoint CRC.
+// tools, label / input / augmentation preparation, the test-time augmentation image pyramid, the
+// bootstrap threshold and the checkpoint CRC.
 #include "net.h"
 
 using namespace segnet;
@@ -170,6 +171,15 @@ int seg_prepare_images_crop(const uint8_t* raw, int n, int src_h, int src_w, int
   hipError_t e = launch_prepare_images(raw, n, src_h, src_w, resized_h, resized_w, crop_y, crop_x,
                                        H, W, out, (hipStream_t)stream);
   return e == hipSuccess ? 0 : hip_fail(nullptr, e, "seg_prepare_images_crop");
+}
+
+int seg_resize_images(const float* in, int n, int H, int W, int h_out, int w_out, int flip,
+                      float* out, void* stream) {
+  if (n < 0 || H <= 0 || W <= 0 || h_out <= 0 || w_out <= 0 || (n > 0 && (!in || !out)))
+    return set_err(nullptr, -EINVAL, "seg_resize_images: bad arguments");
+  if (flip < 0 || flip > 1) return set_err(nullptr, -EINVAL, "seg_resize_images: flip = %d (0 or 1)", flip);
+  hipError_t e = launch_resize_images(in, n, H, W, h_out, w_out, flip, out, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : hip_fail(nullptr, e, "seg_resize_images");
 }
 
 int seg_prepare_labels(const uint8_t* raw, int n, int src_h, int src_w, int H, int W,

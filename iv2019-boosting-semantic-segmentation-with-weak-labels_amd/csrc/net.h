@@ -26,6 +26,7 @@
 #include "labels.h"
 #include "optim.h"
 #include "pool.h"
+#include "tta.h"
 
 namespace segnet {
 

@@ -195,6 +195,9 @@ int make_pool_grids(seg_ctx* c, GridSpec& g, int H, int W, const std::vector<std
   memset(&g, 0, sizeof(g));
   g.n = (int)win.size();
   for (int i = 0; i < g.n; ++i) {
+    if (win[i].first < 1 || win[i].second < 1)   // PSP: dims // 6 of a map under 6 x 6
+      return set_err(&c->err, -EINVAL, "the %d x %d feature map is too small for the pyramid's "
+                     "pooling grids (PSP needs at least 6 x 6: an input of 48 x 48)", H, W);
     g.kh[i] = win[i].first; g.kw[i] = win[i].second;
     g.kr[i] = (H - g.kh[i]) / g.kh[i] + 1;
     g.kc[i] = (W - g.kw[i]) / g.kw[i] + 1;

@@ -103,9 +103,9 @@ def define_estimator(mode, features, labels, model_fn, config, params):
     proimages = features['proimages']
     _, _, predictions = model_fn(mode, proimages, labels, config, params)
     if mode == ModeKeys.EVAL:
-        return _eval_spec(predictions, labels, config, params)
+        return _eval_spec(predictions, labels, config, params, proimages)
     if mode == ModeKeys.PREDICT:
-        return _predict_spec(predictions, features, params)
+        return _predict_spec(predictions, features, params, config)
     global_step = get_or_create_global_step()
     ctx = predictions['_context']
     # fp16 storage: dynamic loss scaling (the scale must be set before the loss seeds the
@@ -138,12 +138,15 @@ def define_estimator(mode, features, labels, model_fn, config, params):
     return EstimatorSpec(mode, predictions, losses['total'], train_op, losses)
 
 
-def _eval_spec(predictions, labels, config, params):
+def _eval_spec(predictions, labels, config, params, proimages=None):
     """EVAL branch (define_estimator_hierarchical.py:161-200): zero losses, decisions mapped
     to evaluation cids, optionally void-replaced, nearest-neighbour resized to the label
     size, and the streaming confusion matrix of this batch (labels rows, decisions columns),
-    max(tcids2ecids) + 1 classes. All of it runs on the device (seg_predict, seg_confusion)."""
+    max(tcids2ecids) + 1 classes. All of it runs on the device (seg_predict, seg_confusion).
+    With params.tta_scales / params.tta_flip the decisions come from the probabilities averaged
+    over the scaled / mirrored forwards instead (estimator/tta.py, seg_tta_decisions)."""
     import torch
+    from estimator.tta import attach_predictions, driver_for
     from utils.utils import _replacevoids
     if getattr(params, 'preserve_aspect_ratio', False):
         raise NotImplementedError('evaluation with preserving aspect ratio is not implemented.')
@@ -152,7 +155,12 @@ def _eval_spec(predictions, labels, config, params):
     prolabels = labels['prolabels']
     tcids2ecids = list(params.training_cids2evaluation_cids)
     decs = torch.empty(prolabels.shape, dtype=torch.int32, device=prolabels.device)
-    ctx.predict(tcids2ecids, decs, replace_voids=bool(getattr(params, 'replace_voids', False)))
+    replace = bool(getattr(params, 'replace_voids', False))
+    tta = driver_for(ctx, config, params, ModeKeys.EVAL)
+    if tta is None:
+        ctx.predict(tcids2ecids, decs, replace_voids=replace)
+    else:
+        attach_predictions(predictions, tta, tta.decisions(proimages, tcids2ecids, decs, replace))
     nc = max(_replacevoids(tcids2ecids)) + 1
     cm = torch.empty((nc, nc), dtype=torch.int32, device=prolabels.device)
     ctx.confusion(prolabels.to(torch.int32).contiguous(), decs, nc, cm)
@@ -162,7 +170,7 @@ def _eval_spec(predictions, labels, config, params):
                          {'confusion_matrix': cm})
 
 
-def _predict_spec(predictions, features, params):
+def _predict_spec(predictions, features, params, config=None):
     """PREDICT branch (define_estimator_hierarchical.py:203-238): decisions in TRAINING cids
     (the reference leaves the inference-cid mapping commented out, :226-227), resized to
     (height_system, width_system) when both are set, else to the raw image size, else kept at
@@ -170,8 +178,12 @@ def _predict_spec(predictions, features, params):
     bilinear align-corners); --replace_voids then takes the top-2 of the RESIZED l1
     probabilities (_replace_voids, :530-630), all in one device launch. The full-resolution
     logits / probabilities / per-head decisions stay lazy entries of the model's predictions
-    (materialised on first access)."""
+    (materialised on first access). With params.tta_scales / params.tta_flip the decisions come
+    from the averaged probabilities (estimator/tta.py); --replace_voids then replaces at the
+    network size before the resize (mode 1 of seg_predict: the resize-first order is not defined
+    for averaged probabilities)."""
     import torch
+    from estimator.tta import attach_predictions, driver_for
     ctx = predictions['_context']
     img = features['proimages']
     n, h_net, w_net = img.shape[0], img.shape[1], img.shape[2]
@@ -181,7 +193,12 @@ def _predict_spec(predictions, features, params):
         size = (int(raw.shape[1]), int(raw.shape[2])) if raw is not None else (h_net, w_net)
     replace = bool(getattr(params, 'replace_voids', False))
     decs = torch.empty((n,) + tuple(size), dtype=torch.int32, device=img.device)
-    ctx.predict(list(range(params.output_Nclasses)), decs, replace_voids=replace, order="predict")
+    tta = driver_for(ctx, config, params, ModeKeys.PREDICT)
+    if tta is None:
+        ctx.predict(list(range(params.output_Nclasses)), decs, replace_voids=replace, order="predict")
+    else:
+        attach_predictions(predictions, tta,
+                           tta.decisions(img, list(range(params.output_Nclasses)), decs, replace))
     out = predictions
     out['decisions'] = decs
     for k in ('rawimages', 'rawimagespaths'):

@@ -2,7 +2,8 @@
 
 Same command line: ``python evaluate.py <log_dir> <Neval> <training_problem_def_path>
 {cityscapes,vistas} [--ckpt_path P | --eval_all_ckpts] [--evaluation_problem_def_path P]
-[--replace_voids] [--Nb N]`` plus the model flags. The reference's own ``__main__`` raises
+[--replace_voids] [--Nb N]`` plus the model flags and ``[--tta_scales S [S ...]] [--tta_flip]``
+(multi-scale and flip inference, estimator/tta.py; off by default). The reference's own ``__main__`` raises
 NotImplementedError (evaluate.py:81-83); here ``main`` runs: checkpoints written by train.py
 (``<log_dir>/model.ckpt-<step>.pt``) are evaluated on the eval input_fn (seeded synthetic
 Cityscapes-shaped batches, or ``--tfrecords_path`` TFRecords of KEYS2FEATURES_v5 examples), the confusion matrices are
@@ -39,7 +40,8 @@ def _add_extra_args(args):
     args.batch_norm_decay = 1.0
 
 
-def main(argv, max_steps=None):
+def build_arguments():
+    from estimator.tta import add_tta_arguments
     ssargs = SemanticSegmentationArguments(mode=ModeKeys.EVAL)
     add_model_arguments(ssargs.argparser)
     ssargs.argparser.add_argument('per_pixel_dataset_name', type=str,
@@ -47,6 +49,12 @@ def main(argv, max_steps=None):
     ssargs.argparser.add_argument('--eval_res_dir', type=str, default=None)
     # the reference hard-codes its TFRecord path; without one, seeded synthetic batches
     ssargs.argparser.add_argument('--tfrecords_path', type=str, default=None)
+    add_tta_arguments(ssargs.argparser)
+    return ssargs
+
+
+def main(argv, max_steps=None):
+    ssargs = build_arguments()
     args = ssargs.parse_args(argv)
     _add_extra_args(args)
     system = SemanticSegmentation({'eval': tfrecord_eval_fn if args.tfrecords_path else eval_fn},

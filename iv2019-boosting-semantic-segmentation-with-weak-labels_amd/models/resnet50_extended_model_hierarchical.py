@@ -155,6 +155,7 @@ class Predictions(MutableMapping):
         self._ctx = ctx
         self._forward_id = getattr(ctx, 'forward_count', 0)
         self._c = (53, 12, 5) if dataset == 'vistas' else (14, 7, 3)
+        self._tta = None   # set by use_tta
         _, _, logits = ctx.outputs()
         n, h, w = logits.shape[0], ctx.cfg.height, ctx.cfg.width
         self._shape = (n, h, w)
@@ -184,9 +185,23 @@ class Predictions(MutableMapping):
             self._store[f'{head}_decisions'] = hd[..., i]
             lo += c
 
+    def use_tta(self, materialise):
+        """Test-time augmentation (estimator/tta.py): the lazy entries come from the averaged
+        probabilities. ``materialise()`` returns the ``*_probabilities`` / ``*_decisions``
+        entries; averaged logits do not exist, so ``*_logits`` raise KeyError and are not
+        listed by iteration."""
+        self._tta = materialise
+
     def __getitem__(self, k):
         if k in LAZY_KEYS and k not in self._store:
-            self._materialise()
+            if self._tta is None:
+                self._materialise()
+            elif k.endswith('_logits'):
+                raise KeyError(f'{k}: test-time augmentation (--tta_scales / --tta_flip) averages '
+                               'probabilities over several forwards; there are no full-resolution '
+                               'logits of the average (the *_probabilities entries hold it)')
+            else:
+                self._store.update(self._tta())
         return self._store[k]
 
     def __setitem__(self, k, v):
@@ -195,11 +210,16 @@ class Predictions(MutableMapping):
     def __delitem__(self, k):
         del self._store[k]
 
+    def _lazy_keys(self):
+        if self._tta is None:
+            return LAZY_KEYS
+        return tuple(k for k in LAZY_KEYS if not k.endswith('_logits'))
+
     def __iter__(self):
-        return iter(list(dict.fromkeys(LAZY_KEYS + tuple(self._store))))
+        return iter(list(dict.fromkeys(self._lazy_keys() + tuple(self._store))))
 
     def __len__(self):
-        return len(set(LAZY_KEYS) | set(self._store))
+        return len(set(self._lazy_keys()) | set(self._store))
 
     def materialised(self):
         """The entries computed so far (no launch): a plain dict."""

@@ -3,7 +3,8 @@
 Same command line: ``python predict.py <log_dir> <training_problem_def_path> <predict_dir>
 [--ckpt_path P] [--inference_problem_def_path P] [--replace_voids] [--Nb N]
 [--export_lids_images] [--export_color_decisions] [--export_overlapped_color_decisions]
-[--results_dir D]`` plus the model flags and the dataset name. Images of ``predict_dir``
+[--results_dir D]`` plus the model flags, the dataset name and ``[--tta_scales S [S ...]]
+[--tta_flip]`` (multi-scale and flip inference, estimator/tta.py; off by default). Images of ``predict_dir``
 (png / jpg / ppm, input_cityscapes.py:248-260) are decoded on the host (PIL, as the reference
 does), preprocessed on the device (``seg_prepare_images``: convert_image_dtype, bilinear resize
 to the network size, [-1, 1) centring, input_cityscapes.py:262-269), run through the PREDICT
@@ -69,10 +70,17 @@ def _add_predict_arguments(argparser):
     a('--results_dir', type=str, default=None)
 
 
-def main(argv, max_steps=None):
+def build_arguments():
+    from estimator.tta import add_tta_arguments
     ssargs = SemanticSegmentationArguments(mode=ModeKeys.PREDICT)
     add_model_arguments(ssargs.argparser)
     _add_predict_arguments(ssargs.argparser)
+    add_tta_arguments(ssargs.argparser)
+    return ssargs
+
+
+def main(argv, max_steps=None):
+    ssargs = build_arguments()
     s = ssargs.parse_args(argv)
     s.regularization_weight = 0.0   # predict.py:168-181
     s.batch_norm_decay = 1.0

@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = [
     "seg_crc32c", "seg_prepare_images", "seg_prepare_labels", "seg_prepare_images_crop",
     "seg_bbox_labels_flip", "seg_augment_workspace", "seg_augment_images", "seg_augment_labels", "seg_augment_profile",
     "seg_augment_profile_blur", "seg_set_bootstrap", "seg_op_bootstrap_threshold",
+    "seg_resize_images", "seg_tta_decisions",
 ]
 
 # int (*seg_allreduce_fn)(void* user, float* buf, int64_t n, void* stream)
@@ -87,6 +88,14 @@ class BnBwdArgs(ctypes.Structure):
         ("dzscale", _FP), ("dshift", _FP), ("beta", _FP), ("cs_part", _FP),
         ("part", _FP), ("dgamma", _FP), ("dbeta", _FP),
     ]
+
+
+TTA_MAX_ENTRIES = 16   # SEG_TTA_MAX_ENTRIES
+
+
+class TtaEntry(ctypes.Structure):
+    """seg_tta_entry (include/seg_hip.h); logits is a device address"""
+    _fields_ = [("logits", _VP), ("h_low", _INT), ("w_low", _INT), ("ld", _INT), ("flip", _INT)]
 
 
 def _load():
@@ -177,6 +186,9 @@ def _load():
         "seg_counter": (ip, [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64)]),
         "seg_set_bootstrap": (ip, [vp, ip]),
         "seg_op_bootstrap_threshold": (ip, [vp, i64, i64, ctypes.POINTER(f), ctypes.POINTER(i64), vp]),
+        "seg_resize_images": (ip, [vp, ip, ip, ip, ip, ip, ip, vp, vp]),
+        "seg_tta_decisions": (ip, [vp, ctypes.POINTER(TtaEntry), ip, ctypes.POINTER(ctypes.c_int32),
+                                   ip, ip, ip, ip, vp, vp, vp]),
     }
     override = "SEG_HIP_LIB" in os.environ   # A/B builds of older commits may lack new entries
     for name, (res, args) in sig.items():
@@ -250,6 +262,7 @@ class SegContext:
         check(LIB.seg_bind_buffers(self.h, _ptr(self.params), _ptr(self.grads),
                                    _ptr(self.momentum), _ptr(self.ema), _ptr(self.moving)), self.h)
         self.param_info = self._param_info()
+        self.params_version = 0   # refreshes of the compute copies so far (params_updated)
 
     # ---- parameters -----------------------------------------------------------------
     def _param_info(self) -> List[ParamInfo]:
@@ -279,7 +292,14 @@ class SegContext:
                 self._buffer_for(p)[p.offset:p.offset + p.numel].copy_(v.to(self.device))
         if self.ema is not None:
             self.ema.copy_(self.params)
+        self.params_updated(stream)
+
+    def params_updated(self, stream=None):
+        """seg_params_updated: refresh the compute copies after ``params`` / ``moving`` were
+        written. ``params_version`` counts these refreshes: holders of a copy of the parameters
+        (the test-time augmentation contexts) compare it to know when to copy again."""
         check(LIB.seg_params_updated(self.h, _stream(stream)), self.h)
+        self.params_version += 1
 
     def named(self, buffer: str = "params") -> Dict[str, np.ndarray]:
         """Host copies of named tensors of params/grads/momentum/ema."""
@@ -359,6 +379,40 @@ class SegContext:
                                  f"contiguous device tensor [{n}, {hw[0]}, {hw[1]}, ...]")
         check(LIB.seg_full_predictions(self.h, _ptr(logits), _ptr(probs), _ptr(head_decisions),
                                        _ptr(decisions), _stream(stream)), self.h)
+
+    def tta_decisions(self, entries, cid_map, out, replace_voids=False, mean_probs=None,
+                      stream=None):
+        """seg_tta_decisions: decisions from the probabilities averaged over ``entries``, a list
+        of (logits, flip): logits a contiguous device f32 [N, h_low, w_low, ld] (ld >= c1 + c2 +
+        c3 is the pixel stride) of one scale's forward, flip True when that forward saw the
+        mirrored image. ``cid_map`` / ``out`` / ``replace_voids`` as in ``predict`` (mode
+        "eval"; the "predict" order is not defined for averaged probabilities). ``mean_probs``:
+        optional device f32 [N, H, W, c1 + c2 + c3] for the mean probabilities; needs out's
+        size to be the network size. The context's own logits are not read."""
+        import torch
+        n = self.cfg.nb_pp + self.cfg.nb_pb + self.cfg.nb_pi
+        if not (out.dtype == torch.int32 and out.dim() == 3 and out.is_contiguous()
+                and out.shape[0] == n and out.is_cuda):
+            raise ValueError(f"decisions buffer must be a contiguous device int32 [{n}, Ho, Wo]")
+        if len(entries) > TTA_MAX_ENTRIES:
+            raise ValueError(f"{len(entries)} entries: at most {TTA_MAX_ENTRIES} "
+                             "(scales x flips) per decision launch")
+        arr = (TtaEntry * max(len(entries), 1))()
+        for i, (lg, flip) in enumerate(entries):
+            if not (lg.dtype == torch.float32 and lg.is_cuda and lg.is_contiguous()
+                    and lg.dim() == 4 and lg.shape[0] == n):
+                raise ValueError(f"entry {i}: logits must be a contiguous device float32 "
+                                 f"[{n}, h_low, w_low, ld], got {tuple(lg.shape)} {lg.dtype}")
+            arr[i] = TtaEntry(lg.data_ptr(), int(lg.shape[1]), int(lg.shape[2]), int(lg.shape[3]),
+                              int(flip))
+        if mean_probs is not None and not (mean_probs.dtype == torch.float32 and mean_probs.is_cuda
+                                           and mean_probs.is_contiguous() and mean_probs.dim() == 4
+                                           and mean_probs.shape[0] == n):
+            raise ValueError(f"mean_probs must be a contiguous device float32 [{n}, H, W, C]")
+        m = (ctypes.c_int32 * len(cid_map))(*[int(v) for v in cid_map])
+        check(LIB.seg_tta_decisions(self.h, arr, len(entries), m, len(cid_map), int(replace_voids),
+                                    int(out.shape[1]), int(out.shape[2]), _ptr(mean_probs),
+                                    _ptr(out), _stream(stream)), self.h)
 
     def backward(self, stream=None):
         check(LIB.seg_backward(self.h, _stream(stream)), self.h)
@@ -543,6 +597,21 @@ class SegContext:
             self.close()
         except Exception:
             pass
+
+
+def resize_images(x, h: int, w: int, flip: bool = False, stream=None):
+    """seg_resize_images: contiguous device float32 [n, H, W, 3] -> [n, h, w, 3] by TF 1.12's
+    legacy bilinear resize (align_corners = False) of the image, mirrored in x first when
+    ``flip``. Equal sizes copy (or mirror) bit for bit."""
+    import torch
+    if not (x.dtype == torch.float32 and x.is_cuda and x.is_contiguous() and x.dim() == 4
+            and x.shape[3] == 3):
+        raise ValueError(f"images must be a contiguous device float32 [n, H, W, 3], got "
+                         f"{tuple(x.shape)} {x.dtype}")
+    out = torch.empty((x.shape[0], int(h), int(w), 3), dtype=torch.float32, device=x.device)
+    check(LIB.seg_resize_images(_ptr(x), int(x.shape[0]), int(x.shape[1]), int(x.shape[2]), int(h),
+                                int(w), int(flip), _ptr(out), _stream(stream)))
+    return out
 
 
 def bootstrap_threshold(values, k: int, stream=None):

@@ -88,7 +88,11 @@ class SemanticSegmentationArguments(object):
         p.add_argument('training_problem_def_path', type=str)
         p.add_argument('predict_dir', type=str, default=None)
         p.add_argument('--inference_problem_def_path', type=str, default=None)
-        p.add_argument('--replace_voids', action='store_true')
+        p.add_argument('--replace_voids', action='store_true',
+                       help='replace void decisions by the best non-void l1 class, from the top-2 '
+                            'of the l1 probabilities resized to the output size; with test-time '
+                            'augmentation (--tta_scales / --tta_flip) from the top-2 of the '
+                            'averaged l1 probabilities at the network size, before the resize')
         p.add_argument('--Nb', type=int, default=1)
         p.add_argument('--restore_emas', action='store_true')
         p.add_argument('--train_void_class', action='store_true')
