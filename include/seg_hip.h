@@ -251,6 +251,57 @@ int seg_tta_decisions(seg_ctx* ctx, const seg_tta_entry* entries, int n_entries,
                       const int32_t* cid_map, int n_map, int replace_voids, int out_h, int out_w,
                       float* mean_probs_out, int32_t* decisions_out, void* stream);
 
+/* sliding-window inference (the [tile] ... [stich] of the reference's system sketch,
+ * utils/utils.py above --height_system; it builds neither, the semantics are fixed here). The
+ * caller prepares the batch at a canvas of canvas_h x canvas_w >= the network size H x W, runs one
+ * moving-statistics forward of the SAME context per entry -- the H x W window of the canvas at
+ * origin (ys[iy], xs[ix]), mirrored in x or not -- and hands the entries' low-resolution logits
+ * to one decision launch. The window grid is the product ys x xs; the entry order is rows of ys
+ * outermost, then xs, then, with flip, the unflipped entry followed by the mirrored one:
+ * entry (iy * nx + ix) * (1 + flip) + mirrored.
+ * seg_window_images: out[b][y][x][c] = in[b][y0 + y][x0 + (flip ? W - 1 - x : x)][c] for fp32
+ *   [n][Hc][Wc][3] -> [n][H][W][3]: a copy, bit for bit. -EINVAL with a seg_last_error text
+ *   naming the function, and no launch, for a null pointer with n > 0, n < 0, a size < 1, a
+ *   window that is not inside the canvas, or flip outside 0..1.
+ * seg_window_decisions: N, H, W (the network size = the window size) and the head tables come
+ *   from ctx; the context's own logits are not read. logits is a host array of ny * nx *
+ *   (1 + flip) device pointers in entry order, each fp32 [N][h_low][w_low][ld] (channels l1 | l2
+ *   vehicle | l2 human, ld >= c1 + c2 + c3 the pixel stride). For canvas pixel (n, Y, X) and each
+ *   entry whose window contains it, in entry order: (y, x) = (Y - y0, X - x0); u =
+ *   ResizeBilinear(align_corners = True) of the entry's logits to H x W at (y, x), or at column
+ *   W - 1 - x for a mirrored entry; p = the per-head softmax of u, both exactly as
+ *   seg_tta_decisions forms them; sum = the first covering entry's p plus the others' in entry
+ *   order in fp32; k = the number of covering entries; mean = sum * r_k with r_k the correctly
+ *   rounded fp32 1 / k (1.0f / (float)k divided on the host, the bits seg_tta_decisions uses for
+ *   k entries). Decisions on the sums exactly as in seg_tta_decisions: per-head first-maximum
+ *   argmax -> hierarchical fusion -> cid_map (-1 -> max + 1) -> replace_voids = 1: the stable
+ *   top-2 of the l1 sums -> NEAREST_NEIGHBOR align_corners resize from the CANVAS to out_h x
+ *   out_w; only the canvas pixels the output pixels select are computed, and no full-resolution
+ *   tensor is written. decisions_out: device int32 [N][out_h][out_w]. mean_probs_out: optional
+ *   (NULL skips it) device fp32 [N][canvas_h][canvas_w][c1 + c2 + c3], 16-byte aligned; needs
+ *   out_h x out_w = canvas_h x canvas_w.
+ *   With canvas = network size (ys = xs = {0}) the outputs are bitwise those of
+ *   seg_tta_decisions on the same one or two entries; with windows that do not overlap, every
+ *   window's part of the outputs is bitwise seg_tta_decisions on that window's entries alone.
+ *   -EINVAL with a seg_last_error text naming the function, and no launch, for: a null ctx,
+ *   logits array, logits entry, ys, xs, cid_map or decisions_out; ny or nx < 1; more than
+ *   SEG_WIN_MAX_ENTRIES entries; h_low or w_low < 1; ld < c1 + c2 + c3; flip outside 0..1;
+ *   replace_voids outside 0..1 (2, seg_predict's PREDICT order, is not defined for averaged
+ *   probabilities); a canvas smaller than the network size on either axis; an origin list that
+ *   is not strictly increasing, does not start at 0, leaves a gap (ys[i + 1] > ys[i] + H) or
+ *   whose last window does not end at the canvas edge (ys[ny - 1] + H != canvas_h), likewise xs
+ *   with W and canvas_w -- together they give every canvas pixel k >= 1; a cid map of the wrong
+ *   length or with an entry < -1; an output size < 1; mean_probs_out misaligned or given with an
+ *   output size other than the canvas. */
+#define SEG_WIN_MAX_ENTRIES 64
+int seg_window_images(const float* in, int n, int Hc, int Wc, int y0, int x0, int H, int W,
+                      int flip, float* out, void* stream);
+int seg_window_decisions(seg_ctx* ctx, const float* const* logits, int h_low, int w_low, int ld,
+                         const int* ys, int ny, const int* xs, int nx, int flip,
+                         int canvas_h, int canvas_w, const int32_t* cid_map, int n_map,
+                         int replace_voids, int out_h, int out_w,
+                         float* mean_probs_out, int32_t* decisions_out, void* stream);
+
 /* input preprocessing (input_cityscapes.py:66-96,190-209), after the host
  * decodes TFRecord -> tf.train.Example -> PNG (input_pipelines/tfrecords.py):
  * seg_prepare_images: raw uint8 [n][src_h][src_w][3] -> convert_image_dtype -> bilinear

@@ -271,6 +271,90 @@ int seg_tta_decisions(seg_ctx* c, const seg_tta_entry* entries, int n_entries,
   return 0;
 }
 
+int seg_window_decisions(seg_ctx* c, const float* const* logits, int h_low, int w_low, int ld,
+                         const int* ys, int ny, const int* xs, int nx, int flip,
+                         int canvas_h, int canvas_w, const int32_t* cid_map, int n_map,
+                         int replace_voids, int out_h, int out_w,
+                         float* mean_probs_out, int32_t* decisions_out, void* stream) {
+  const char* who = "seg_window_decisions";
+  if (!c) return set_err(nullptr, -EINVAL, "%s: null ctx", who);
+  if (!logits || !ys || !xs || !cid_map || !decisions_out)
+    return set_err(&c->err, -EINVAL, "%s: null logits / ys / xs / cid_map / decisions_out", who);
+  if (ny < 1 || nx < 1)
+    return set_err(&c->err, -EINVAL, "%s: %d x %d windows (at least 1 x 1)", who, ny, nx);
+  if (flip < 0 || flip > 1) return set_err(&c->err, -EINVAL, "%s: flip = %d (0 or 1)", who, flip);
+  static_assert(SEG_WIN_MAX_ENTRIES == WIN_MAX_ENTRIES, "entry table size");
+  const long n_entries = (long)ny * nx * (1 + flip);
+  if (n_entries > SEG_WIN_MAX_ENTRIES)
+    return set_err(&c->err, -EINVAL, "%s: %d x %d windows%s are %ld entries (1..%d)", who, ny, nx,
+                   flip ? " with flip" : "", n_entries, SEG_WIN_MAX_ENTRIES);
+  const seg_cfg& g = c->cfg;
+  const LossTables& t = c->tables;
+  const int ct = t.c1 + t.c2 + t.c3;
+  if (h_low < 1 || w_low < 1)
+    return set_err(&c->err, -EINVAL, "%s: low-resolution size %dx%d", who, h_low, w_low);
+  if (ld < ct) return set_err(&c->err, -EINVAL, "%s: pixel stride %d < %d channels", who, ld, ct);
+  if (replace_voids == 2)
+    return set_err(&c->err, -EINVAL, "%s: replace_voids = 2 (the PREDICT order on resized "
+                   "probabilities) is not defined for averaged probabilities; use 1", who);
+  if (replace_voids < 0 || replace_voids > 1)
+    return set_err(&c->err, -EINVAL, "%s: replace_voids = %d (0 or 1)", who, replace_voids);
+  if (canvas_h < g.height || canvas_w < g.width)
+    return set_err(&c->err, -EINVAL, "%s: the canvas %dx%d is smaller than the network size %dx%d",
+                   who, canvas_h, canvas_w, g.height, g.width);
+  // strictly increasing from 0, no gap, the last window flush with the edge: every canvas pixel
+  // is covered, and every window lies inside the canvas
+  auto origins = [&](const char* name, const int* o, int n, int len, int canvas) {
+    if (o[0] != 0) return set_err(&c->err, -EINVAL, "%s: %s[0] = %d (must be 0)", who, name, o[0]);
+    for (int i = 0; i + 1 < n; ++i) {
+      if (o[i + 1] <= o[i])
+        return set_err(&c->err, -EINVAL, "%s: %s[%d] = %d after %d: origins must increase strictly",
+                       who, name, i + 1, o[i + 1], o[i]);
+      if (o[i + 1] > o[i] + len)
+        return set_err(&c->err, -EINVAL, "%s: %s[%d] = %d leaves a gap after the window at %d of "
+                       "length %d", who, name, i + 1, o[i + 1], o[i], len);
+    }
+    if ((long)o[n - 1] + len != canvas)
+      return set_err(&c->err, -EINVAL, "%s: the last window %s[%d] = %d of length %d does not end "
+                     "at the canvas edge %d", who, name, n - 1, o[n - 1], len, canvas);
+    return 0;
+  };
+  if (int rc = origins("ys", ys, ny, g.height, canvas_h)) return rc;
+  if (int rc = origins("xs", xs, nx, g.width, canvas_w)) return rc;
+  if (n_map != t.n_pp)
+    return set_err(&c->err, -EINVAL, "%s: cid map has %d entries, the model has %d training classes",
+                   who, n_map, t.n_pp);
+  if (out_h < 1 || out_w < 1)
+    return set_err(&c->err, -EINVAL, "%s: bad output size %dx%d", who, out_h, out_w);
+  if (mean_probs_out && (reinterpret_cast<uintptr_t>(mean_probs_out) & 15))
+    return set_err(&c->err, -EINVAL, "%s: mean_probs_out must be 16-byte aligned", who);
+  if (mean_probs_out && (out_h != canvas_h || out_w != canvas_w))
+    return set_err(&c->err, -EINVAL, "%s: mean_probs_out needs the output size %dx%d to be the "
+                   "canvas size %dx%d", who, out_h, out_w, canvas_h, canvas_w);
+  WinArgs a{};
+  for (int i = 0; i < (int)n_entries; ++i) {
+    if (!logits[i]) return set_err(&c->err, -EINVAL, "%s: entry %d: null logits", who, i);
+    a.logits[i] = logits[i];
+  }
+  for (int i = 0; i < ny; ++i) a.ys[i] = ys[i];
+  for (int i = 0; i < nx; ++i) a.xs[i] = xs[i];
+  for (int k = 1; k <= WIN_MAX_ENTRIES; ++k) a.rk[k] = 1.0f / (float)k;   // host IEEE division
+  a.ny = ny; a.nx = nx; a.flip = flip;
+  a.hl = h_low; a.wl = w_low; a.ld = ld;
+  a.N = c->logits.N; a.H = g.height; a.W = g.width; a.Hc = canvas_h; a.Wc = canvas_w;
+  a.Ho = out_h; a.Wo = out_w;
+  a.replace_voids = replace_voids; a.n_map = n_map;
+  a.probs = mean_probs_out; a.out = decisions_out;
+  int mx = -1;
+  for (int i = 0; i < n_map; ++i) mx = std::max(mx, (int)cid_map[i]);
+  for (int i = 0; i < n_map; ++i) {   // utils._replacevoids: -1 -> max + 1
+    if (cid_map[i] < -1) return set_err(&c->err, -EINVAL, "%s: cid_map[%d] = %d", who, i, cid_map[i]);
+    a.map[i] = cid_map[i] == -1 ? mx + 1 : cid_map[i];
+  }
+  HIPCALL(c, launch_window_decisions(a, t, (hipStream_t)stream));
+  return 0;
+}
+
 int seg_backward(seg_ctx* c, void* stream) {
   NEED_BOUND(c);
   Step S{c, (hipStream_t)stream, c->dt};

@@ -1,6 +1,6 @@
 // The context-free entries of the C ABI (include/seg_hip.h): single conv launches for tests and
 // tools, label / input / augmentation preparation, the test-time augmentation image pyramid, the
-// bootstrap threshold and the checkpoint CRC.
+// sliding-window extraction, the bootstrap threshold and the checkpoint CRC.
 #include "net.h"
 
 using namespace segnet;
@@ -180,6 +180,19 @@ int seg_resize_images(const float* in, int n, int H, int W, int h_out, int w_out
   if (flip < 0 || flip > 1) return set_err(nullptr, -EINVAL, "seg_resize_images: flip = %d (0 or 1)", flip);
   hipError_t e = launch_resize_images(in, n, H, W, h_out, w_out, flip, out, (hipStream_t)stream);
   return e == hipSuccess ? 0 : hip_fail(nullptr, e, "seg_resize_images");
+}
+
+int seg_window_images(const float* in, int n, int Hc, int Wc, int y0, int x0, int H, int W,
+                      int flip, float* out, void* stream) {
+  const char* who = "seg_window_images";
+  if (n < 0 || Hc <= 0 || Wc <= 0 || H <= 0 || W <= 0 || (n > 0 && (!in || !out)))
+    return set_err(nullptr, -EINVAL, "%s: bad arguments", who);
+  if (y0 < 0 || x0 < 0 || (long)y0 + H > Hc || (long)x0 + W > Wc)
+    return set_err(nullptr, -EINVAL, "%s: the %dx%d window at (%d, %d) is not inside the %dx%d canvas",
+                   who, H, W, y0, x0, Hc, Wc);
+  if (flip < 0 || flip > 1) return set_err(nullptr, -EINVAL, "%s: flip = %d (0 or 1)", who, flip);
+  hipError_t e = launch_window_images(in, n, Hc, Wc, y0, x0, H, W, flip, out, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : hip_fail(nullptr, e, who);
 }
 
 int seg_prepare_labels(const uint8_t* raw, int n, int src_h, int src_w, int H, int W,

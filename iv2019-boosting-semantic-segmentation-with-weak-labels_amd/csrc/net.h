@@ -27,6 +27,7 @@
 #include "optim.h"
 #include "pool.h"
 #include "tta.h"
+#include "window.h"
 
 namespace segnet {
 

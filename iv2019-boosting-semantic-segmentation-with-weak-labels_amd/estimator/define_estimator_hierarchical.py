@@ -144,9 +144,12 @@ def _eval_spec(predictions, labels, config, params, proimages=None):
     size, and the streaming confusion matrix of this batch (labels rows, decisions columns),
     max(tcids2ecids) + 1 classes. All of it runs on the device (seg_predict, seg_confusion).
     With params.tta_scales / params.tta_flip the decisions come from the probabilities averaged
-    over the scaled / mirrored forwards instead (estimator/tta.py, seg_tta_decisions)."""
+    over the scaled / mirrored forwards instead (estimator/tta.py, seg_tta_decisions); with
+    params.window_canvas from the probabilities averaged over the windows of the canvas that
+    proimages then is (estimator/windows.py, seg_window_decisions)."""
     import torch
     from estimator.tta import attach_predictions, driver_for
+    from estimator.windows import attach_window_predictions, driver_for_windows
     from utils.utils import _replacevoids
     if getattr(params, 'preserve_aspect_ratio', False):
         raise NotImplementedError('evaluation with preserving aspect ratio is not implemented.')
@@ -156,8 +159,12 @@ def _eval_spec(predictions, labels, config, params, proimages=None):
     tcids2ecids = list(params.training_cids2evaluation_cids)
     decs = torch.empty(prolabels.shape, dtype=torch.int32, device=prolabels.device)
     replace = bool(getattr(params, 'replace_voids', False))
-    tta = driver_for(ctx, config, params, ModeKeys.EVAL)
-    if tta is None:
+    win = driver_for_windows(ctx, config, params, ModeKeys.EVAL)
+    tta = None if win is not None else driver_for(ctx, config, params, ModeKeys.EVAL)
+    if win is not None:   # --window_canvas: proimages is the canvas, every window a forward
+        attach_window_predictions(predictions, win,
+                                  win.decisions(proimages, tcids2ecids, decs, replace))
+    elif tta is None:
         ctx.predict(tcids2ecids, decs, replace_voids=replace)
     else:
         attach_predictions(predictions, tta, tta.decisions(proimages, tcids2ecids, decs, replace))
@@ -181,9 +188,11 @@ def _predict_spec(predictions, features, params, config=None):
     (materialised on first access). With params.tta_scales / params.tta_flip the decisions come
     from the averaged probabilities (estimator/tta.py); --replace_voids then replaces at the
     network size before the resize (mode 1 of seg_predict: the resize-first order is not defined
-    for averaged probabilities)."""
+    for averaged probabilities). params.window_canvas: the same from the windows of the canvas
+    (estimator/windows.py)."""
     import torch
     from estimator.tta import attach_predictions, driver_for
+    from estimator.windows import attach_window_predictions, driver_for_windows
     ctx = predictions['_context']
     img = features['proimages']
     n, h_net, w_net = img.shape[0], img.shape[1], img.shape[2]
@@ -193,8 +202,12 @@ def _predict_spec(predictions, features, params, config=None):
         size = (int(raw.shape[1]), int(raw.shape[2])) if raw is not None else (h_net, w_net)
     replace = bool(getattr(params, 'replace_voids', False))
     decs = torch.empty((n,) + tuple(size), dtype=torch.int32, device=img.device)
-    tta = driver_for(ctx, config, params, ModeKeys.PREDICT)
-    if tta is None:
+    win = driver_for_windows(ctx, config, params, ModeKeys.PREDICT)
+    tta = None if win is not None else driver_for(ctx, config, params, ModeKeys.PREDICT)
+    if win is not None:   # --window_canvas: img is the canvas, every window a forward
+        attach_window_predictions(predictions, win,
+                                  win.decisions(img, list(range(params.output_Nclasses)), decs, replace))
+    elif tta is None:
         ctx.predict(list(range(params.output_Nclasses)), decs, replace_voids=replace, order="predict")
     else:
         attach_predictions(predictions, tta,

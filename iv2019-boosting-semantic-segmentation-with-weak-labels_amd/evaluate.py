@@ -3,7 +3,8 @@
 Same command line: ``python evaluate.py <log_dir> <Neval> <training_problem_def_path>
 {cityscapes,vistas} [--ckpt_path P | --eval_all_ckpts] [--evaluation_problem_def_path P]
 [--replace_voids] [--Nb N]`` plus the model flags and ``[--tta_scales S [S ...]] [--tta_flip]``
-(multi-scale and flip inference, estimator/tta.py; off by default). The reference's own ``__main__`` raises
+(multi-scale and flip inference, estimator/tta.py; off by default) and ``[--window_canvas HC WC]
+[--window_stride SY SX]`` (sliding-window inference, estimator/windows.py; off by default). The reference's own ``__main__`` raises
 NotImplementedError (evaluate.py:81-83); here ``main`` runs: checkpoints written by train.py
 (``<log_dir>/model.ckpt-<step>.pt``) are evaluated on the eval input_fn (seeded synthetic
 Cityscapes-shaped batches, or ``--tfrecords_path`` TFRecords of KEYS2FEATURES_v5 examples), the confusion matrices are
@@ -27,11 +28,11 @@ from utils.utils import SemanticSegmentationArguments, print_metrics_from_confus
 def tfrecord_eval_fn(config, params):
     """evaluate_input over params.tfrecords_path (input_cityscapes.py:190-240): TFRecord ->
     PNG decode on the host, resize / lids2cids (evaluation problem definition) on the device."""
+    from estimator.windows import input_size
     from input_pipelines.tfrecords import tfrecord_input
     from input_pipelines.utils import get_temp_Nb
     return tfrecord_input(params.tfrecords_path, params.evaluation_problem_def['lids2cids'],
-                          params.height_feature_extractor, params.width_feature_extractor,
-                          get_temp_Nb(config, params.Nb))
+                          *input_size(params), get_temp_Nb(config, params.Nb))
 
 
 def _add_extra_args(args):
@@ -42,6 +43,7 @@ def _add_extra_args(args):
 
 def build_arguments():
     from estimator.tta import add_tta_arguments
+    from estimator.windows import add_window_arguments
     ssargs = SemanticSegmentationArguments(mode=ModeKeys.EVAL)
     add_model_arguments(ssargs.argparser)
     ssargs.argparser.add_argument('per_pixel_dataset_name', type=str,
@@ -50,6 +52,7 @@ def build_arguments():
     # the reference hard-codes its TFRecord path; without one, seeded synthetic batches
     ssargs.argparser.add_argument('--tfrecords_path', type=str, default=None)
     add_tta_arguments(ssargs.argparser)
+    add_window_arguments(ssargs.argparser)
     return ssargs
 
 
@@ -57,6 +60,8 @@ def main(argv, max_steps=None):
     ssargs = build_arguments()
     args = ssargs.parse_args(argv)
     _add_extra_args(args)
+    from estimator.windows import window_settings
+    window_settings(args)   # refuses --tta_scales with --window_canvas before anything is built
     system = SemanticSegmentation({'eval': tfrecord_eval_fn if args.tfrecords_path else eval_fn},
                                   model_fn, args)
     all_metrics = system.evaluate(max_steps=max_steps)

@@ -58,12 +58,13 @@ def batch(seed, nb_pp, nb_pb, nb_pi, h, w):
 def evaluate_input(config, params, seed=1234, device=None):
     """EVAL input_fn in the reference's contract (input_cityscapes.py evaluate_input):
     endless seeded batches of ({'proimages'}, {'prolabels'}) as device tensors, Nb images
-    per rank at the network size, labels at (label_height, label_width) when the settings
-    carry them (default: the network size)."""
+    per rank at the network size (the canvas under --window_canvas), labels at (label_height,
+    label_width) when the settings carry them (default: the images' size)."""
     import torch
+    from estimator.windows import input_size
     from input_pipelines.utils import get_temp_Nb
     nb = get_temp_Nb(config, params.Nb)
-    h, w = params.height_feature_extractor, params.width_feature_extractor
+    h, w = input_size(params)
     hl = getattr(params, 'label_height', None) or h
     wl = getattr(params, 'label_width', None) or w
     dev = device or torch.device('cuda', torch.cuda.current_device())

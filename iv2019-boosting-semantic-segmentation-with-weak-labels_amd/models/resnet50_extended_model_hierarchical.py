@@ -124,6 +124,13 @@ def model(mode, features, labels, config, params):
     infer = not bool(getattr(params, 'batch_norm_accumulate_statistics', mode == ModeKeys.TRAIN))
     if getattr(ctx, 'bn_inference', False) != infer:
         ctx.set_bn_inference(infer)
+    if mode != ModeKeys.TRAIN:
+        # --window_canvas (estimator/windows.py): features is the canvas; the window driver of
+        # the EVAL / PREDICT spec runs every forward, this function runs none
+        from estimator.windows import window_settings
+        if window_settings(params) is not None:
+            return None, {}, Predictions(ctx, params.per_pixel_dataset_name,
+                                         canvas=tuple(features.shape[:3]))
     ctx.forward(features.contiguous())
     return None, {}, Predictions(ctx, params.per_pixel_dataset_name)
 
@@ -150,12 +157,18 @@ class Predictions(MutableMapping):
     of ``SemanticSegmentation.predict`` and ``predict.py`` do), or ``materialised()`` for the
     entries computed so far without a launch."""
 
-    def __init__(self, ctx, dataset='cityscapes'):
+    def __init__(self, ctx, dataset='cityscapes', canvas=None):
         import torch
         self._ctx = ctx
         self._forward_id = getattr(ctx, 'forward_count', 0)
         self._c = (53, 12, 5) if dataset == 'vistas' else (14, 7, 3)
         self._tta = None   # set by use_tta
+        self._windows = canvas is not None   # sliding windows: (n, Hc, Wc), no forward has run
+        if self._windows:
+            self._shape = tuple(int(v) for v in canvas)
+            self._store = {'decisions': torch.zeros(self._shape, dtype=torch.int32, device=ctx.device),
+                           '_context': ctx}
+            return
         _, _, logits = ctx.outputs()
         n, h, w = logits.shape[0], ctx.cfg.height, ctx.cfg.width
         self._shape = (n, h, w)
@@ -189,10 +202,18 @@ class Predictions(MutableMapping):
         """Test-time augmentation (estimator/tta.py): the lazy entries come from the averaged
         probabilities. ``materialise()`` returns the ``*_probabilities`` / ``*_decisions``
         entries; averaged logits do not exist, so ``*_logits`` raise KeyError and are not
-        listed by iteration."""
+        listed by iteration. Sliding windows (estimator/windows.py) use the same hook with the
+        mean probabilities at the canvas size."""
         self._tta = materialise
 
     def __getitem__(self, k):
+        if self._windows and k not in self._store and (
+                k in LAZY_KEYS or k.endswith('_logits_lowres')):
+            if k.endswith('_logits') or k.endswith('_logits_lowres') or self._tta is None:
+                raise KeyError(f'{k}: sliding windows (--window_canvas) average probabilities over '
+                               'the windows that cover a pixel; no forward saw the canvas, so there '
+                               'are no logits of it (the *_probabilities entries hold the average)')
+            self._store.update(self._tta())
         if k in LAZY_KEYS and k not in self._store:
             if self._tta is None:
                 self._materialise()
@@ -211,7 +232,7 @@ class Predictions(MutableMapping):
         del self._store[k]
 
     def _lazy_keys(self):
-        if self._tta is None:
+        if self._tta is None and not self._windows:
             return LAZY_KEYS
         return tuple(k for k in LAZY_KEYS if not k.endswith('_logits'))
 

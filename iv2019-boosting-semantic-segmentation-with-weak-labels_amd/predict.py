@@ -4,7 +4,9 @@ Same command line: ``python predict.py <log_dir> <training_problem_def_path> <pr
 [--ckpt_path P] [--inference_problem_def_path P] [--replace_voids] [--Nb N]
 [--export_lids_images] [--export_color_decisions] [--export_overlapped_color_decisions]
 [--results_dir D]`` plus the model flags, the dataset name and ``[--tta_scales S [S ...]]
-[--tta_flip]`` (multi-scale and flip inference, estimator/tta.py; off by default). Images of ``predict_dir``
+[--tta_flip]`` (multi-scale and flip inference, estimator/tta.py; off by default) and
+``[--window_canvas HC WC] [--window_stride SY SX]`` (sliding-window inference,
+estimator/windows.py; off by default: the images are then prepared at the canvas size). Images of ``predict_dir``
 (png / jpg / ppm, input_cityscapes.py:248-260) are decoded on the host (PIL, as the reference
 does), preprocessed on the device (``seg_prepare_images``: convert_image_dtype, bilinear resize
 to the network size, [-1, 1) centring, input_cityscapes.py:262-269), run through the PREDICT
@@ -39,6 +41,7 @@ def predict_dir_input(config, params):
     'rawimagespaths' lists only the real ones (the export loop zips over it)."""
     import torch
     from PIL import Image
+    from estimator.windows import input_size
     from input_pipelines.tfrecords import prepare_images
     from input_pipelines.utils import get_temp_Nb
     nb = get_temp_Nb(config, params.Nb)
@@ -51,8 +54,7 @@ def predict_dir_input(config, params):
         padded = chunk + [chunk[-1]] * (nb - len(chunk))
         raws = [np.array(Image.open(f).convert('RGB'), dtype=np.uint8) for f in padded]
         raw = torch.from_numpy(np.stack(raws)).to(dev)
-        yield {'proimages': prepare_images(raw, params.height_feature_extractor,
-                                           params.width_feature_extractor),
+        yield {'proimages': prepare_images(raw, *input_size(params)),
                'rawimages': raw, 'rawimagespaths': chunk}, None
 
 
@@ -72,10 +74,12 @@ def _add_predict_arguments(argparser):
 
 def build_arguments():
     from estimator.tta import add_tta_arguments
+    from estimator.windows import add_window_arguments
     ssargs = SemanticSegmentationArguments(mode=ModeKeys.PREDICT)
     add_model_arguments(ssargs.argparser)
     _add_predict_arguments(ssargs.argparser)
     add_tta_arguments(ssargs.argparser)
+    add_window_arguments(ssargs.argparser)
     return ssargs
 
 
@@ -84,6 +88,8 @@ def main(argv, max_steps=None):
     s = ssargs.parse_args(argv)
     s.regularization_weight = 0.0   # predict.py:168-181
     s.batch_norm_decay = 1.0
+    from estimator.windows import window_settings
+    window_settings(s)   # refuses --tta_scales with --window_canvas before anything is built
     if s.plotting or s.plotting_overlapped:
         raise NotImplementedError('live plotting is not built; use the --export_* flags')
     if s.export_lids_images or s.export_color_decisions or s.export_overlapped_color_decisions:

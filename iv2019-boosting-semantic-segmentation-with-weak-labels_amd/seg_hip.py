@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = [
     "seg_bbox_labels_flip", "seg_augment_workspace", "seg_augment_images", "seg_augment_labels", "seg_augment_profile",
     "seg_augment_profile_blur", "seg_set_bootstrap", "seg_op_bootstrap_threshold",
     "seg_resize_images", "seg_tta_decisions",
+    "seg_window_images", "seg_window_decisions",
 ]
 
 # int (*seg_allreduce_fn)(void* user, float* buf, int64_t n, void* stream)
@@ -91,6 +92,7 @@ class BnBwdArgs(ctypes.Structure):
 
 
 TTA_MAX_ENTRIES = 16   # SEG_TTA_MAX_ENTRIES
+WIN_MAX_ENTRIES = 64   # SEG_WIN_MAX_ENTRIES
 
 
 class TtaEntry(ctypes.Structure):
@@ -189,6 +191,10 @@ def _load():
         "seg_resize_images": (ip, [vp, ip, ip, ip, ip, ip, ip, vp, vp]),
         "seg_tta_decisions": (ip, [vp, ctypes.POINTER(TtaEntry), ip, ctypes.POINTER(ctypes.c_int32),
                                    ip, ip, ip, ip, vp, vp, vp]),
+        "seg_window_images": (ip, [vp, ip, ip, ip, ip, ip, ip, ip, ip, vp, vp]),
+        "seg_window_decisions": (ip, [vp, ctypes.POINTER(vp), ip, ip, ip, ctypes.POINTER(ip), ip,
+                                      ctypes.POINTER(ip), ip, ip, ip, ip,
+                                      ctypes.POINTER(ctypes.c_int32), ip, ip, ip, ip, vp, vp, vp]),
     }
     override = "SEG_HIP_LIB" in os.environ   # A/B builds of older commits may lack new entries
     for name, (res, args) in sig.items():
@@ -414,6 +420,50 @@ class SegContext:
                                     int(out.shape[1]), int(out.shape[2]), _ptr(mean_probs),
                                     _ptr(out), _stream(stream)), self.h)
 
+    def window_decisions(self, entries, ys, xs, flip, canvas_hw, cid_map, out,
+                         replace_voids=False, mean_probs=None, stream=None):
+        """seg_window_decisions: decisions from the probabilities averaged over the windows that
+        cover each pixel of a canvas. ``entries``: contiguous device f32 [N, h_low, w_low, ld]
+        tensors of one shape, the low-resolution logits of this context's forwards on the
+        windows at origins ``ys`` x ``xs`` of the ``canvas_hw`` canvas, in entry order (rows of
+        ys outermost, then xs, then with ``flip`` the unflipped entry followed by the mirrored
+        one). ``cid_map`` / ``out`` / ``replace_voids`` as in ``tta_decisions``; the nearest
+        resize to out's size starts from the canvas. ``mean_probs``: optional device f32
+        [N, Hc, Wc, c1 + c2 + c3]; needs out's size to be the canvas size. The context's own
+        logits are not read."""
+        import torch
+        n = self.cfg.nb_pp + self.cfg.nb_pb + self.cfg.nb_pi
+        if not (out.dtype == torch.int32 and out.dim() == 3 and out.is_contiguous()
+                and out.shape[0] == n and out.is_cuda):
+            raise ValueError(f"decisions buffer must be a contiguous device int32 [{n}, Ho, Wo]")
+        ys, xs = [int(v) for v in ys], [int(v) for v in xs]
+        want = len(ys) * len(xs) * (2 if flip else 1)
+        if want > WIN_MAX_ENTRIES:
+            raise ValueError(f"{len(ys)} x {len(xs)} windows{' with flip' if flip else ''} are "
+                             f"{want} entries: at most {WIN_MAX_ENTRIES} per decision launch")
+        if len(entries) != want or want == 0:
+            raise ValueError(f"{len(entries)} entries for {len(ys)} x {len(xs)} windows"
+                             f"{' with flip' if flip else ''}: expected {want} (at least 1)")
+        shape = tuple(entries[0].shape)
+        for i, lg in enumerate(entries):
+            if not (lg.dtype == torch.float32 and lg.is_cuda and lg.is_contiguous()
+                    and lg.dim() == 4 and lg.shape[0] == n and tuple(lg.shape) == shape):
+                raise ValueError(f"entry {i}: logits must be a contiguous device float32 "
+                                 f"[{n}, h_low, w_low, ld] of the first entry's shape {shape}, "
+                                 f"got {tuple(lg.shape)} {lg.dtype}")
+        if mean_probs is not None and not (mean_probs.dtype == torch.float32 and mean_probs.is_cuda
+                                           and mean_probs.is_contiguous() and mean_probs.dim() == 4
+                                           and mean_probs.shape[0] == n):
+            raise ValueError(f"mean_probs must be a contiguous device float32 [{n}, Hc, Wc, C]")
+        ptrs = (_VP * want)(*[lg.data_ptr() for lg in entries])
+        m = (ctypes.c_int32 * len(cid_map))(*[int(v) for v in cid_map])
+        check(LIB.seg_window_decisions(self.h, ptrs, shape[1], shape[2], shape[3],
+                                       (_INT * len(ys))(*ys), len(ys), (_INT * len(xs))(*xs), len(xs),
+                                       int(bool(flip)), int(canvas_hw[0]), int(canvas_hw[1]), m,
+                                       len(cid_map), int(replace_voids), int(out.shape[1]),
+                                       int(out.shape[2]), _ptr(mean_probs), _ptr(out),
+                                       _stream(stream)), self.h)
+
     def backward(self, stream=None):
         check(LIB.seg_backward(self.h, _stream(stream)), self.h)
 
@@ -611,6 +661,22 @@ def resize_images(x, h: int, w: int, flip: bool = False, stream=None):
     out = torch.empty((x.shape[0], int(h), int(w), 3), dtype=torch.float32, device=x.device)
     check(LIB.seg_resize_images(_ptr(x), int(x.shape[0]), int(x.shape[1]), int(x.shape[2]), int(h),
                                 int(w), int(flip), _ptr(out), _stream(stream)))
+    return out
+
+
+def window_images(x, y0: int, x0: int, H: int, W: int, flip: bool = False, stream=None):
+    """seg_window_images: the H x W window at (y0, x0) of a contiguous device float32 canvas
+    [n, Hc, Wc, 3], mirrored in x when ``flip``: a bitwise copy [n, H, W, 3]."""
+    import torch
+    if not (x.dtype == torch.float32 and x.is_cuda and x.is_contiguous() and x.dim() == 4
+            and x.shape[3] == 3):
+        raise ValueError(f"images must be a contiguous device float32 [n, Hc, Wc, 3], got "
+                         f"{tuple(x.shape)} {x.dtype}")
+    if int(H) < 1 or int(W) < 1:
+        raise ValueError(f"window size {H} x {W} must be positive")
+    out = torch.empty((x.shape[0], int(H), int(W), 3), dtype=torch.float32, device=x.device)
+    check(LIB.seg_window_images(_ptr(x), int(x.shape[0]), int(x.shape[1]), int(x.shape[2]), int(y0),
+                                int(x0), int(H), int(W), int(flip), _ptr(out), _stream(stream)))
     return out
 
 

@@ -92,7 +92,8 @@ class SemanticSegmentationArguments(object):
                        help='replace void decisions by the best non-void l1 class, from the top-2 '
                             'of the l1 probabilities resized to the output size; with test-time '
                             'augmentation (--tta_scales / --tta_flip) from the top-2 of the '
-                            'averaged l1 probabilities at the network size, before the resize')
+                            'averaged l1 probabilities at the network size, before the resize; '
+                            'with sliding windows (--window_canvas) likewise at the canvas size')
         p.add_argument('--Nb', type=int, default=1)
         p.add_argument('--restore_emas', action='store_true')
         p.add_argument('--train_void_class', action='store_true')
