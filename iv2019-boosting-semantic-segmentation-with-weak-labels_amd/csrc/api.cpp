@@ -175,6 +175,45 @@ int seg_set_bn_inference(seg_ctx* c, int on) {
   return 0;
 }
 
+// utils._replacevoids on the caller's cid map: -1 -> max + 1; anything below -1 is refused.
+// who prefixes the message ("who: ") where the entry names itself in its errors.
+static int normalise_cid_map(seg_ctx* c, const char* who, const int32_t* cid_map, int n_map,
+                             int* map) {
+  int mx = -1;
+  for (int i = 0; i < n_map; ++i) mx = std::max(mx, (int)cid_map[i]);
+  for (int i = 0; i < n_map; ++i) {
+    if (cid_map[i] < -1)
+      return set_err(&c->err, -EINVAL, "%s%scid_map[%d] = %d", who ? who : "", who ? ": " : "", i,
+                     cid_map[i]);
+    map[i] = cid_map[i] == -1 ? mx + 1 : cid_map[i];
+  }
+  return 0;
+}
+
+// What the multi-entry heads (seg_tta_decisions, seg_window_decisions) ask of replace_voids, the
+// cid map's length, the output size and mean_probs_out, which needs the output to have the size
+// probabilities are averaged at: avg_h x avg_w, "the <avg_name> size" in the message.
+static int check_averaged_head(seg_ctx* c, const char* who, int replace_voids, int n_map, int out_h,
+                               int out_w, const float* mean_probs_out, const char* avg_name,
+                               int avg_h, int avg_w) {
+  if (replace_voids == 2)
+    return set_err(&c->err, -EINVAL, "%s: replace_voids = 2 (the PREDICT order on resized "
+                   "probabilities) is not defined for averaged probabilities; use 1", who);
+  if (replace_voids < 0 || replace_voids > 1)
+    return set_err(&c->err, -EINVAL, "%s: replace_voids = %d (0 or 1)", who, replace_voids);
+  if (n_map != c->tables.n_pp)
+    return set_err(&c->err, -EINVAL, "%s: cid map has %d entries, the model has %d training classes",
+                   who, n_map, c->tables.n_pp);
+  if (out_h < 1 || out_w < 1)
+    return set_err(&c->err, -EINVAL, "%s: bad output size %dx%d", who, out_h, out_w);
+  if (mean_probs_out && (reinterpret_cast<uintptr_t>(mean_probs_out) & 15))
+    return set_err(&c->err, -EINVAL, "%s: mean_probs_out must be 16-byte aligned", who);
+  if (mean_probs_out && (out_h != avg_h || out_w != avg_w))
+    return set_err(&c->err, -EINVAL, "%s: mean_probs_out needs the output size %dx%d to be the "
+                   "%s size %dx%d", who, out_h, out_w, avg_name, avg_h, avg_w);
+  return 0;
+}
+
 int seg_predict(seg_ctx* c, const int32_t* cid_map, int n_map, int replace_voids, int out_h,
                 int out_w, int32_t* decisions_out, void* stream) {
   NEED_BOUND(c);
@@ -191,12 +230,7 @@ int seg_predict(seg_ctx* c, const int32_t* cid_map, int n_map, int replace_voids
   a.logits = c->head_in; a.N = c->logits.N; a.Hl = c->logits.H; a.Wl = c->logits.W;
   a.ldl = c->ldl; a.H = g.height; a.W = g.width; a.Ho = out_h; a.Wo = out_w;
   a.replace_voids = replace_voids; a.n_map = n_map; a.out = decisions_out;
-  int mx = -1;
-  for (int i = 0; i < n_map; ++i) mx = std::max(mx, (int)cid_map[i]);
-  for (int i = 0; i < n_map; ++i) {   // utils._replacevoids: -1 -> max + 1
-    if (cid_map[i] < -1) return set_err(&c->err, -EINVAL, "cid_map[%d] = %d", i, cid_map[i]);
-    a.map[i] = cid_map[i] == -1 ? mx + 1 : cid_map[i];
-  }
+  if (int r = normalise_cid_map(c, nullptr, cid_map, n_map, a.map)) return r;
   HIPCALL(c, launch_eval_decisions(a, c->tables, (hipStream_t)stream));
   return 0;
 }
@@ -229,21 +263,9 @@ int seg_tta_decisions(seg_ctx* c, const seg_tta_entry* entries, int n_entries,
   const seg_cfg& g = c->cfg;
   const LossTables& t = c->tables;
   const int ct = t.c1 + t.c2 + t.c3;
-  if (replace_voids == 2)
-    return set_err(&c->err, -EINVAL, "%s: replace_voids = 2 (the PREDICT order on resized "
-                   "probabilities) is not defined for averaged probabilities; use 1", who);
-  if (replace_voids < 0 || replace_voids > 1)
-    return set_err(&c->err, -EINVAL, "%s: replace_voids = %d (0 or 1)", who, replace_voids);
-  if (n_map != t.n_pp)
-    return set_err(&c->err, -EINVAL, "%s: cid map has %d entries, the model has %d training classes",
-                   who, n_map, t.n_pp);
-  if (out_h < 1 || out_w < 1)
-    return set_err(&c->err, -EINVAL, "%s: bad output size %dx%d", who, out_h, out_w);
-  if (mean_probs_out && (reinterpret_cast<uintptr_t>(mean_probs_out) & 15))
-    return set_err(&c->err, -EINVAL, "%s: mean_probs_out must be 16-byte aligned", who);
-  if (mean_probs_out && (out_h != g.height || out_w != g.width))
-    return set_err(&c->err, -EINVAL, "%s: mean_probs_out needs the output size %dx%d to be the "
-                   "network size %dx%d", who, out_h, out_w, g.height, g.width);
+  if (int r = check_averaged_head(c, who, replace_voids, n_map, out_h, out_w, mean_probs_out, "network",
+                                  g.height, g.width))
+    return r;
   TtaArgs a{};
   for (int i = 0; i < n_entries; ++i) {
     const seg_tta_entry& e = entries[i];
@@ -261,12 +283,7 @@ int seg_tta_decisions(seg_ctx* c, const seg_tta_entry* entries, int n_entries,
   a.N = c->logits.N; a.H = g.height; a.W = g.width; a.Ho = out_h; a.Wo = out_w;
   a.replace_voids = replace_voids; a.n_map = n_map;
   a.probs = mean_probs_out; a.out = decisions_out;
-  int mx = -1;
-  for (int i = 0; i < n_map; ++i) mx = std::max(mx, (int)cid_map[i]);
-  for (int i = 0; i < n_map; ++i) {   // utils._replacevoids: -1 -> max + 1
-    if (cid_map[i] < -1) return set_err(&c->err, -EINVAL, "%s: cid_map[%d] = %d", who, i, cid_map[i]);
-    a.map[i] = cid_map[i] == -1 ? mx + 1 : cid_map[i];
-  }
+  if (int r = normalise_cid_map(c, who, cid_map, n_map, a.map)) return r;
   HIPCALL(c, launch_tta_decisions(a, t, (hipStream_t)stream));
   return 0;
 }
@@ -294,11 +311,6 @@ int seg_window_decisions(seg_ctx* c, const float* const* logits, int h_low, int 
   if (h_low < 1 || w_low < 1)
     return set_err(&c->err, -EINVAL, "%s: low-resolution size %dx%d", who, h_low, w_low);
   if (ld < ct) return set_err(&c->err, -EINVAL, "%s: pixel stride %d < %d channels", who, ld, ct);
-  if (replace_voids == 2)
-    return set_err(&c->err, -EINVAL, "%s: replace_voids = 2 (the PREDICT order on resized "
-                   "probabilities) is not defined for averaged probabilities; use 1", who);
-  if (replace_voids < 0 || replace_voids > 1)
-    return set_err(&c->err, -EINVAL, "%s: replace_voids = %d (0 or 1)", who, replace_voids);
   if (canvas_h < g.height || canvas_w < g.width)
     return set_err(&c->err, -EINVAL, "%s: the canvas %dx%d is smaller than the network size %dx%d",
                    who, canvas_h, canvas_w, g.height, g.width);
@@ -321,16 +333,9 @@ int seg_window_decisions(seg_ctx* c, const float* const* logits, int h_low, int 
   };
   if (int rc = origins("ys", ys, ny, g.height, canvas_h)) return rc;
   if (int rc = origins("xs", xs, nx, g.width, canvas_w)) return rc;
-  if (n_map != t.n_pp)
-    return set_err(&c->err, -EINVAL, "%s: cid map has %d entries, the model has %d training classes",
-                   who, n_map, t.n_pp);
-  if (out_h < 1 || out_w < 1)
-    return set_err(&c->err, -EINVAL, "%s: bad output size %dx%d", who, out_h, out_w);
-  if (mean_probs_out && (reinterpret_cast<uintptr_t>(mean_probs_out) & 15))
-    return set_err(&c->err, -EINVAL, "%s: mean_probs_out must be 16-byte aligned", who);
-  if (mean_probs_out && (out_h != canvas_h || out_w != canvas_w))
-    return set_err(&c->err, -EINVAL, "%s: mean_probs_out needs the output size %dx%d to be the "
-                   "canvas size %dx%d", who, out_h, out_w, canvas_h, canvas_w);
+  if (int r = check_averaged_head(c, who, replace_voids, n_map, out_h, out_w, mean_probs_out, "canvas",
+                                  canvas_h, canvas_w))
+    return r;
   WinArgs a{};
   for (int i = 0; i < (int)n_entries; ++i) {
     if (!logits[i]) return set_err(&c->err, -EINVAL, "%s: entry %d: null logits", who, i);
@@ -345,12 +350,7 @@ int seg_window_decisions(seg_ctx* c, const float* const* logits, int h_low, int 
   a.Ho = out_h; a.Wo = out_w;
   a.replace_voids = replace_voids; a.n_map = n_map;
   a.probs = mean_probs_out; a.out = decisions_out;
-  int mx = -1;
-  for (int i = 0; i < n_map; ++i) mx = std::max(mx, (int)cid_map[i]);
-  for (int i = 0; i < n_map; ++i) {   // utils._replacevoids: -1 -> max + 1
-    if (cid_map[i] < -1) return set_err(&c->err, -EINVAL, "%s: cid_map[%d] = %d", who, i, cid_map[i]);
-    a.map[i] = cid_map[i] == -1 ? mx + 1 : cid_map[i];
-  }
+  if (int r = normalise_cid_map(c, who, cid_map, n_map, a.map)) return r;
   HIPCALL(c, launch_window_decisions(a, t, (hipStream_t)stream));
   return 0;
 }

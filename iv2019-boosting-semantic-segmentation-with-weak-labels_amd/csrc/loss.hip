@@ -493,214 +493,6 @@ __global__ void confusion_kernel(const int* __restrict__ lab, const int* __restr
     if (h[i]) atomicAdd(&cm[i], h[i]);
 }
 
-
-// TF 1.12 ResizeNearestNeighbor(align_corners=True) source index (legacy scaler, roundf)
-__device__ __forceinline__ int nn_src(int o, int n_in, int n_out) {
-  const float scale = n_out > 1 ? (float)(n_in - 1) / (float)(n_out - 1) : (float)n_in / (float)n_out;
-  const int i = (int)roundf((float)o * scale);
-  return i < n_in - 1 ? i : n_in - 1;
-}
-
-// one thread per output pixel; the 4 source cells of the bilinear footprint are read from
-// HBM/L2 directly (eval is one forward per batch: this kernel is ~0.1 % of it)
-template <int C1, int C2, int C3>
-__global__ __launch_bounds__(256) void eval_decisions_kernel(EvalArgs a, LossTables t) {
-  constexpr int CT = C1 + C2 + C3;
-  const long total = (long)a.N * a.Ho * a.Wo;
-  for (long id = (long)blockIdx.x * blockDim.x + threadIdx.x; id < total;
-       id += (long)gridDim.x * blockDim.x) {
-    const int xo = (int)(id % a.Wo);
-    const int yo = (int)((id / a.Wo) % a.Ho);
-    const int n = (int)(id / ((long)a.Wo * a.Ho));
-    const int h = nn_src(yo, a.H, a.Ho), w = nn_src(xo, a.W, a.Wo);
-    int ylo, yhi, xlo, xhi;
-    float yl, xl;
-    lerp_of(h, a.Hl, a.H, ylo, yhi, yl);
-    lerp_of(w, a.Wl, a.W, xlo, xhi, xl);
-    const float* base = a.logits + (size_t)n * a.Hl * a.Wl * a.ldl;
-    const float* tl = base + ((size_t)ylo * a.Wl + xlo) * a.ldl;
-    const float* tr = base + ((size_t)ylo * a.Wl + xhi) * a.ldl;
-    const float* bl = base + ((size_t)yhi * a.Wl + xlo) * a.ldl;
-    const float* br = base + ((size_t)yhi * a.Wl + xhi) * a.ldl;
-    float p[CT];
-#pragma unroll
-    for (int c = 0; c < CT; ++c) {
-      float top = tl[c] + (tr[c] - tl[c]) * xl;
-      float bot = bl[c] + (br[c] - bl[c]) * xl;
-      p[c] = top + (bot - top) * yl;
-    }
-    // softmax per head (the same arithmetic as the loss head), argmax first max
-    auto softmax = [&](int c0, int nc) {
-      float m = p[c0];
-#pragma unroll
-      for (int c = 1; c < nc; ++c) m = fmaxf(m, p[c0 + c]);
-      float s = 0.f;
-#pragma unroll
-      for (int c = 0; c < nc; ++c) { p[c0 + c] = __expf(p[c0 + c] - m); s += p[c0 + c]; }
-      const float rs = 1.f / s;
-#pragma unroll
-      for (int c = 0; c < nc; ++c) p[c0 + c] = p[c0 + c] * rs;
-    };
-    softmax(0, C1);
-    softmax(C1, C2);
-    softmax(C1 + C2, C3);
-    int d1 = 0;
-    float b1 = p[0];
-#pragma unroll
-    for (int c = 1; c < C1; ++c) if (p[c] > b1) { b1 = p[c]; d1 = c; }
-    int d;
-    if (d1 == t.cid_l1_vehicle) {
-      int b = 0;
-      float bv = p[C1];
-#pragma unroll
-      for (int c = 1; c < C2; ++c) if (p[C1 + c] > bv) { bv = p[C1 + c]; b = c; }
-      d = t.veh_to_common[b];
-    } else if (d1 == t.cid_l1_human) {
-      int b = 0;
-      float bv = p[C1 + C2];
-#pragma unroll
-      for (int c = 1; c < C3; ++c) if (p[C1 + C2 + c] > bv) { bv = p[C1 + C2 + c]; b = c; }
-      d = t.hum_to_common[b];
-    } else {
-      d = t.l1_to_common[d1];
-    }
-    d = a.map[d];   // tf.gather(ocids2ncids, decs)
-    if (a.replace_voids == 2) {
-      // PREDICT order (define_estimator_hierarchical.py:227-231): _resize_predictions first --
-      // decisions NEAREST (above), l1_probabilities ResizeBilinear(align_corners) from the
-      // network to the output size -- then _replace_voids on the RESIZED probabilities
-      // (top_k(k=2), stable; void = decision C1 - 1). The 4 network-resolution pixels of the
-      // output pixel's footprint get their l1 softmax from the low-res logits as above.
-      int y0, y1, x0, x1;
-      float ylp, xlp;
-      lerp_of(yo, a.H, a.Ho, y0, y1, ylp);
-      lerp_of(xo, a.W, a.Wo, x0, x1, xlp);
-      float q[4][C1];
-      const int ys[2] = {y0, y1}, xs[2] = {x0, x1};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        int ya, yb, xa, xb;
-        float ly, lx;
-        lerp_of(ys[k >> 1], a.Hl, a.H, ya, yb, ly);
-        lerp_of(xs[k & 1], a.Wl, a.W, xa, xb, lx);
-        const float* ta = base + ((size_t)ya * a.Wl + xa) * a.ldl;
-        const float* tb = base + ((size_t)ya * a.Wl + xb) * a.ldl;
-        const float* ba = base + ((size_t)yb * a.Wl + xa) * a.ldl;
-        const float* bb = base + ((size_t)yb * a.Wl + xb) * a.ldl;
-        float m = -INFINITY;
-#pragma unroll
-        for (int c = 0; c < C1; ++c) {
-          float top = ta[c] + (tb[c] - ta[c]) * lx;
-          float bot = ba[c] + (bb[c] - ba[c]) * lx;
-          q[k][c] = top + (bot - top) * ly;
-          m = fmaxf(m, q[k][c]);
-        }
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < C1; ++c) { q[k][c] = __expf(q[k][c] - m); s += q[k][c]; }
-        const float rs = 1.f / s;
-#pragma unroll
-        for (int c = 0; c < C1; ++c) q[k][c] = q[k][c] * rs;
-      }
-      int i1 = -1, i2 = -1;
-      float v1 = 0.f, v2 = 0.f;
-#pragma unroll
-      for (int c = 0; c < C1; ++c) {
-        const float top = q[0][c] + (q[1][c] - q[0][c]) * xlp;
-        const float bot = q[2][c] + (q[3][c] - q[2][c]) * xlp;
-        const float v = top + (bot - top) * ylp;
-        if (i1 < 0 || v > v1) { i2 = i1; v2 = v1; i1 = c; v1 = v; }
-        else if (i2 < 0 || v > v2) { i2 = c; v2 = v; }
-      }
-      d = d == C1 - 1 ? i2 : i1;
-    } else if (a.replace_voids) {
-      // top_k(l1_probabilities, 2) (stable: equal values keep the lower index first);
-      // l1_probabilities keep C1 channels (the segment-sum remap does not apply to them)
-      int d2 = -1;
-      float b2 = 0.f;
-#pragma unroll
-      for (int c = 0; c < C1; ++c)
-        if (c != d1 && (d2 < 0 || p[c] > b2)) { b2 = p[c]; d2 = c; }
-      d = d == C1 - 1 ? d2 : d1;
-    }
-    a.out[id] = d;
-  }
-}
-// The model's full-resolution `predictions` (hierarchical.py:84-130), materialised on demand:
-// per network-resolution pixel the align-corners bilinear logits of the three heads, their
-// softmax, per-head argmax and the fused common-cid decision. Same arithmetic as the loss
-// head / eval kernel (one thread per pixel, the 4 low-res source cells read through L2); every
-// output is optional. Stores are per pixel runs of CT floats (float4 where CT % 4 == 0).
-template <int C1, int C2, int C3>
-__global__ __launch_bounds__(256) void full_predictions_kernel(FullPredArgs a, LossTables t) {
-  constexpr int CT = C1 + C2 + C3;
-  const long total = (long)a.N * a.H * a.W;
-  for (long id = (long)blockIdx.x * blockDim.x + threadIdx.x; id < total;
-       id += (long)gridDim.x * blockDim.x) {
-    const int w = (int)(id % a.W);
-    const int h = (int)((id / a.W) % a.H);
-    const int n = (int)(id / ((long)a.W * a.H));
-    int ylo, yhi, xlo, xhi;
-    float yl, xl;
-    lerp_of(h, a.Hl, a.H, ylo, yhi, yl);
-    lerp_of(w, a.Wl, a.W, xlo, xhi, xl);
-    const float* base = a.logits + (size_t)n * a.Hl * a.Wl * a.ldl;
-    const float* tl = base + ((size_t)ylo * a.Wl + xlo) * a.ldl;
-    const float* tr = base + ((size_t)ylo * a.Wl + xhi) * a.ldl;
-    const float* bl = base + ((size_t)yhi * a.Wl + xlo) * a.ldl;
-    const float* br = base + ((size_t)yhi * a.Wl + xhi) * a.ldl;
-    float p[CT];
-#pragma unroll
-    for (int c = 0; c < CT; ++c) {
-      float top = tl[c] + (tr[c] - tl[c]) * xl;
-      float bot = bl[c] + (br[c] - bl[c]) * xl;
-      p[c] = top + (bot - top) * yl;
-    }
-    auto store = [&](float* dst) {
-      float* o = dst + (size_t)id * CT;
-      if constexpr (CT % 4 == 0) {
-#pragma unroll
-        for (int c = 0; c < CT; c += 4)
-          *reinterpret_cast<float4*>(o + c) = make_float4(p[c], p[c + 1], p[c + 2], p[c + 3]);
-      } else {
-#pragma unroll
-        for (int c = 0; c < CT; ++c) o[c] = p[c];
-      }
-    };
-    if (a.logits_out) store(a.logits_out);
-    auto softmax = [&](int c0, int nc) {
-      float m = p[c0];
-#pragma unroll
-      for (int c = 1; c < nc; ++c) m = fmaxf(m, p[c0 + c]);
-      float s = 0.f;
-#pragma unroll
-      for (int c = 0; c < nc; ++c) { p[c0 + c] = __expf(p[c0 + c] - m); s += p[c0 + c]; }
-      const float rs = 1.f / s;
-#pragma unroll
-      for (int c = 0; c < nc; ++c) p[c0 + c] = p[c0 + c] * rs;
-    };
-    softmax(0, C1);
-    softmax(C1, C2);
-    softmax(C1 + C2, C3);
-    if (a.probs_out) store(a.probs_out);
-    auto argmax = [&](int c0, int nc) {   // tf.argmax: first maximum
-      int b = 0;
-      float bv = p[c0];
-#pragma unroll
-      for (int c = 1; c < nc; ++c) if (p[c0 + c] > bv) { bv = p[c0 + c]; b = c; }
-      return b;
-    };
-    const int d1 = argmax(0, C1), dv = argmax(C1, C2), dh = argmax(C1 + C2, C3);
-    if (a.head_decs_out) {
-      int* o = a.head_decs_out + (size_t)id * 3;
-      o[0] = d1; o[1] = dv; o[2] = dh;
-    }
-    if (a.decs_out)
-      a.decs_out[id] = d1 == t.cid_l1_vehicle ? t.veh_to_common[dv]
-                     : d1 == t.cid_l1_human ? t.hum_to_common[dh] : t.l1_to_common[d1];
-  }
-}
-
 // Per-pixel l1 loss map of the strong images (bootstrapped loss, launch_l1_loss_map): one thread
 // per full-resolution pixel, the 4 low-res source cells read through L2, the l1 channels only.
 // The same expressions as loss_head_kernel (lerp_of, top/bot lerp, max, __expf sum, logf), so the
@@ -836,33 +628,5 @@ hipError_t launch_confusion(const int* labels, const int* decisions, long n, int
   if (g > 1024) g = 1024;
   hipLaunchKernelGGL(confusion_kernel, dim3((int)g), dim3(256), 0, s, labels, decisions, n,
                      num_classes, cm);
-  return hipGetLastError();
-}
-
-hipError_t launch_eval_decisions(const EvalArgs& a, const LossTables& t, hipStream_t s) {
-  const long total = (long)a.N * a.Ho * a.Wo;
-  if (total <= 0) return hipSuccess;
-  long g = (total + 255) / 256;
-  if (g > 8192) g = 8192;
-  if (t.c1 == 14 && t.c2 == 7 && t.c3 == 3)
-    hipLaunchKernelGGL((eval_decisions_kernel<14, 7, 3>), dim3((int)g), dim3(256), 0, s, a, t);
-  else if (t.c1 == 53 && t.c2 == 12 && t.c3 == 5)
-    hipLaunchKernelGGL((eval_decisions_kernel<53, 12, 5>), dim3((int)g), dim3(256), 0, s, a, t);
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
-}
-
-hipError_t launch_full_predictions(const FullPredArgs& a, const LossTables& t, hipStream_t s) {
-  const long total = (long)a.N * a.H * a.W;
-  if (total <= 0) return hipSuccess;
-  long g = (total + 255) / 256;
-  if (g > 16384) g = 16384;
-  if (t.c1 == 14 && t.c2 == 7 && t.c3 == 3)
-    hipLaunchKernelGGL((full_predictions_kernel<14, 7, 3>), dim3((int)g), dim3(256), 0, s, a, t);
-  else if (t.c1 == 53 && t.c2 == 12 && t.c3 == 5)
-    hipLaunchKernelGGL((full_predictions_kernel<53, 12, 5>), dim3((int)g), dim3(256), 0, s, a, t);
-  else
-    return hipErrorInvalidValue;
   return hipGetLastError();
 }

@@ -20,6 +20,7 @@
 #include "input.h"
 #include "augment.h"
 #include "conv.h"
+#include "decide.h"
 #include "deconv.h"
 #include "gn.h"
 #include "loss.h"

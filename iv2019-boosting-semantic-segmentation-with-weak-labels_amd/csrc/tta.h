@@ -3,10 +3,10 @@
 //   an image pyramid on the device: fp32 [n][H][W][3] -> legacy bilinear (align_corners = False,
 //     the arithmetic of input.h's image resize) of the optionally mirrored image;
 //   a decision head over several sets of low-resolution logits: per selected network pixel the
-//     align-corners bilinear logits and per-head softmax of every entry (the eval kernel's
-//     expressions, loss.hip), summed in entry order, then the eval kernel's argmax / hierarchical
-//     fusion / cid map / void replacement / nearest resize on the sums. No full-resolution
-//     intermediate is written unless the mean probabilities are asked for.
+//     align-corners bilinear logits and per-head softmax of every entry (decision_head.h, the
+//     calls the eval kernel of decide.hip makes), summed in entry order, then the eval kernel's
+//     argmax / hierarchical fusion / cid map / void replacement / nearest resize on the sums. No
+//     full-resolution intermediate is written unless the mean probabilities are asked for.
 #pragma once
 #include "loss.h"
 

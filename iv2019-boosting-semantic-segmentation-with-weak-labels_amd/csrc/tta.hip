@@ -1,15 +1,14 @@
 // Test-time augmentation kernels (see tta.h).
 //
-// The decision head has the eval kernel's shape (loss.hip): one thread per output pixel, the four
-// low-resolution cells of each entry read through L2, and a register accumulator of the CT
-// probability sums next to the CT live values of the entry being added. lerp_of, nn_src, the
-// top / bot lerp and the softmax are loss.hip's, so that one unflipped entry gives the bits
-// seg_predict and seg_full_predictions give. The one difference in the text: the fused
-// multiply-adds loss.hip gets from the compiler's default contraction (in_f - lo as
-// fma(o, scale, -lo), each lerp as one fma; read off full_predictions_kernel's ISA) are written
-// out here. Left to the compiler, the entry loop puts o * scale and the subtraction of the row
-// weight into different basic blocks, the two are not fused, and the last bits differ.
+// The decision head has the eval kernel's shape (decide.hip): one thread per output pixel, the
+// four low-resolution cells of each entry read through L2, and a register accumulator of the CT
+// probability sums next to the CT live values of the entry being added. The arithmetic is
+// decision_head.h's, the same calls the eval kernels make, so that one unflipped entry gives
+// seg_full_predictions' bits and seg_predict's decisions; its fused multiply-adds are explicit because,
+// left to the compiler, the entry loop puts o * scale and the subtraction of the row weight into
+// different basic blocks and the two are not fused.
 #include "tta.h"
+#include "decision_head.h"
 
 namespace {
 
@@ -17,21 +16,7 @@ constexpr int TTA_THREADS = 256;
 
 // ---- multi-entry decision head ---------------------------------------------------------
 
-__device__ __forceinline__ void lerp_of(int o, int n_in, int n_out, int& lo, int& hi, float& l) {
-  // TF ResizeBilinear legacy scaler, align_corners=True
-  const float scale = n_out > 1 ? (float)(n_in - 1) / (float)(n_out - 1) : 0.f;
-  const float fin = (float)o * scale;
-  lo = (int)fin;
-  hi = lo + 1 < n_in - 1 ? lo + 1 : n_in - 1;
-  l = __fmaf_rn((float)o, scale, -(float)lo);   // fin - (float)lo, contracted as in loss.hip
-}
-
-// TF 1.12 ResizeNearestNeighbor(align_corners=True) source index (legacy scaler, roundf)
-__device__ __forceinline__ int nn_src(int o, int n_in, int n_out) {
-  const float scale = n_out > 1 ? (float)(n_in - 1) / (float)(n_out - 1) : (float)n_in / (float)n_out;
-  const int i = (int)roundf((float)o * scale);
-  return i < n_in - 1 ? i : n_in - 1;
-}
+using namespace decision_head;
 
 template <int C1, int C2, int C3>
 __global__ __launch_bounds__(TTA_THREADS) void tta_decisions_kernel(TtaArgs a, LossTables t) {
@@ -52,85 +37,14 @@ __global__ __launch_bounds__(TTA_THREADS) void tta_decisions_kernel(TtaArgs a, L
       lerp_of(h, en.hl, a.H, ylo, yhi, yl);
       lerp_of(en.flip ? a.W - 1 - w : w, en.wl, a.W, xlo, xhi, xl);
       const float* base = en.logits + (size_t)n * en.hl * en.wl * en.ld;
-      const float* tl = base + ((size_t)ylo * en.wl + xlo) * en.ld;
-      const float* tr = base + ((size_t)ylo * en.wl + xhi) * en.ld;
-      const float* bl = base + ((size_t)yhi * en.wl + xlo) * en.ld;
-      const float* br = base + ((size_t)yhi * en.wl + xhi) * en.ld;
       float p[CT];
-#pragma unroll
-      for (int c = 0; c < CT; ++c) {
-        // top = tl + (tr - tl) * xl; bot likewise; top + (bot - top) * yl, one fma each
-        const float top = __fmaf_rn(tr[c] - tl[c], xl, tl[c]);
-        const float bot = __fmaf_rn(br[c] - bl[c], xl, bl[c]);
-        p[c] = __fmaf_rn(bot - top, yl, top);
-      }
-      // softmax per head (the same arithmetic as the loss head and the eval kernel)
-      auto softmax = [&](int c0, int nc) {
-        float m = p[c0];
-#pragma unroll
-        for (int c = 1; c < nc; ++c) m = fmaxf(m, p[c0 + c]);
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < nc; ++c) { p[c0 + c] = __expf(p[c0 + c] - m); s += p[c0 + c]; }
-        const float rs = 1.f / s;
-#pragma unroll
-        for (int c = 0; c < nc; ++c) p[c0 + c] = p[c0 + c] * rs;
-      };
-      softmax(0, C1);
-      softmax(C1, C2);
-      softmax(C1 + C2, C3);
-      if (e == 0) {
-#pragma unroll
-        for (int c = 0; c < CT; ++c) acc[c] = p[c];
-      } else {
-#pragma unroll
-        for (int c = 0; c < CT; ++c) acc[c] = __fadd_rn(acc[c], p[c]);   // the rounded p, not an FMA
-      }
+      bilerp<CT>(p, cells_of(base, ylo, yhi, xlo, xhi, en.wl, en.ld), xl, yl);
+      softmax_heads<C1, C2, C3>(p);
+      accumulate<CT>(acc, p, e == 0);
     }
-    if (a.probs) {   // Ho x Wo = H x W (checked by the caller): id is the network pixel
-      float* o = a.probs + (size_t)id * CT;
-      if constexpr (CT % 4 == 0) {
-#pragma unroll
-        for (int c = 0; c < CT; c += 4)
-          *reinterpret_cast<float4*>(o + c) = make_float4(acc[c] * inv_e, acc[c + 1] * inv_e,
-                                                          acc[c + 2] * inv_e, acc[c + 3] * inv_e);
-      } else {
-#pragma unroll
-        for (int c = 0; c < CT; ++c) o[c] = acc[c] * inv_e;
-      }
-    }
-    // the eval kernel's decision logic on the sums (a positive common factor changes no order)
-    int d1 = 0;
-    float b1 = acc[0];
-#pragma unroll
-    for (int c = 1; c < C1; ++c) if (acc[c] > b1) { b1 = acc[c]; d1 = c; }
-    int d;
-    if (d1 == t.cid_l1_vehicle) {
-      int b = 0;
-      float bv = acc[C1];
-#pragma unroll
-      for (int c = 1; c < C2; ++c) if (acc[C1 + c] > bv) { bv = acc[C1 + c]; b = c; }
-      d = t.veh_to_common[b];
-    } else if (d1 == t.cid_l1_human) {
-      int b = 0;
-      float bv = acc[C1 + C2];
-#pragma unroll
-      for (int c = 1; c < C3; ++c) if (acc[C1 + C2 + c] > bv) { bv = acc[C1 + C2 + c]; b = c; }
-      d = t.hum_to_common[b];
-    } else {
-      d = t.l1_to_common[d1];
-    }
-    d = a.map[d];   // tf.gather(ocids2ncids, decs)
-    if (a.replace_voids) {
-      // top_k(l1 sums, 2) (stable: equal values keep the lower index first)
-      int d2 = -1;
-      float b2 = 0.f;
-#pragma unroll
-      for (int c = 0; c < C1; ++c)
-        if (c != d1 && (d2 < 0 || acc[c] > b2)) { b2 = acc[c]; d2 = c; }
-      d = d == C1 - 1 ? d2 : d1;
-    }
-    a.out[id] = d;
+    // Ho x Wo = H x W (checked by the caller): id is the network pixel
+    if (a.probs) store_ct<CT>(a.probs + (size_t)id * CT, acc, inv_e);
+    a.out[id] = decide<C1, C2, C3>(acc, t, a.map, a.replace_voids);
   }
 }
 
@@ -138,8 +52,8 @@ __global__ __launch_bounds__(TTA_THREADS) void tta_decisions_kernel(TtaArgs a, L
 // From here to the end of the file every operation rounds on its own, as TF's CPU kernel and
 // input.hip do: no FMA contraction, neither in the lerps nor in the index arithmetic (in_f - lo
 // must see the rounded in_f). Equal sizes then give lerp weights of exactly 0 and the output is
-// the (mirrored) input. The decision head above keeps the default contraction of loss.hip, whose
-// bits it reproduces.
+// the (mirrored) input. The decision head above, and decision_head.h with it, stay outside this
+// pragma: their fused multiply-adds are the explicit ones.
 #pragma clang fp contract(off)
 
 // TF 1.12 legacy scaler, align_corners = False (input.hip's lerp_legacy)
@@ -197,13 +111,8 @@ hipError_t launch_resize_images(const float* in, int n, int H, int W, int Ho, in
 hipError_t launch_tta_decisions(const TtaArgs& a, const LossTables& t, hipStream_t s) {
   const long total = (long)a.N * a.Ho * a.Wo;
   if (total <= 0) return hipSuccess;
-  long g = (total + TTA_THREADS - 1) / TTA_THREADS;
-  if (g > 8192) g = 8192;
-  if (t.c1 == 14 && t.c2 == 7 && t.c3 == 3)
-    hipLaunchKernelGGL((tta_decisions_kernel<14, 7, 3>), dim3((int)g), dim3(TTA_THREADS), 0, s, a, t);
-  else if (t.c1 == 53 && t.c2 == 12 && t.c3 == 5)
-    hipLaunchKernelGGL((tta_decisions_kernel<53, 12, 5>), dim3((int)g), dim3(TTA_THREADS), 0, s, a, t);
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
+  const dim3 g((unsigned)std::min((total + TTA_THREADS - 1) / TTA_THREADS, 8192L));
+  return dispatch_heads(t, [&](auto c1, auto c2, auto c3) {
+    hipLaunchKernelGGL((tta_decisions_kernel<c1, c2, c3>), g, dim3(TTA_THREADS), 0, s, a, t);
+  });
 }

@@ -4,9 +4,9 @@
 //     mirrored in x, copied bit for bit;
 //   a decision head over the low-resolution logits of a separable grid of windows: per selected
 //     canvas pixel the align-corners bilinear logits and per-head softmax of every window that
-//     covers it (tta.hip's expressions), summed in entry order, times the rounded 1 / k of the k
-//     covering entries, then tta.hip's argmax / hierarchical fusion / cid map / void replacement /
-//     nearest resize from the canvas. No full-resolution intermediate is written unless the mean
+//     covers it (decision_head.h, the calls tta.hip makes), summed in entry order, times the
+//     rounded 1 / k of the k covering entries, then the same argmax / hierarchical fusion / cid
+//     map / void replacement / nearest resize from the canvas. No full-resolution intermediate is written unless the mean
 //     probabilities are asked for.
 #pragma once
 #include "loss.h"

@@ -1,13 +1,13 @@
 // Sliding-window inference kernels (see window.h).
 //
-// The decision head is tta.hip's with one more level of geometry: one thread per output pixel,
-// which selects a canvas pixel (Y, X); the windows that cover it are rows iy0..iy1 of ys times
-// columns ix0..ix1 of xs (the origins increase strictly, so both ranges are contiguous), found
-// once per pixel; the pixel takes part in the entries of those ranges only. Inside a window the
-// local position (Y - y0, X - x0) goes through lerp_of, the top / bot lerp and the softmax exactly
-// as tta_decisions_kernel writes them (the same explicit fused multiply-adds, see the head of
-// tta.hip), so a canvas of the network's size gives seg_tta_decisions' bits. The row lerp depends
-// on iy alone and is formed once per row.
+// The decision head has tta.hip's shape with one more level of geometry: one thread per output
+// pixel, which selects a canvas pixel (Y, X); the windows that cover it are rows iy0..iy1 of ys
+// times columns ix0..ix1 of xs (the origins increase strictly, so both ranges are contiguous),
+// found once per pixel; the pixel takes part in the entries of those ranges only. Inside a window
+// the local position (Y - y0, X - x0) goes through the calls of decision_head.h that
+// tta_decisions_kernel makes (lerp_of, the lerp, the softmax, the sum, the decision), so a canvas
+// of the network's size gives seg_tta_decisions' bits. The row lerp depends on iy alone and is
+// formed once per row.
 // The origin and pointer tables are kernel arguments, and the row and column counters are kept
 // uniform over the wave (0..ny, 0..nx with the pixel's range as the predicate) so that the tables
 // come by scalar loads: a wave's pixels share Y and cross a window border in X in few waves, so
@@ -16,26 +16,13 @@
 // every entry's cell loads and measured 2 to 7 % slower. The four low-resolution cells of an
 // entry are read through L2 as in tta.hip.
 #include "window.h"
+#include "decision_head.h"
 
 namespace {
 
+using namespace decision_head;
+
 constexpr int WIN_THREADS = 256;
-
-__device__ __forceinline__ void lerp_of(int o, int n_in, int n_out, int& lo, int& hi, float& l) {
-  // TF ResizeBilinear legacy scaler, align_corners=True (tta.hip's, bit for bit)
-  const float scale = n_out > 1 ? (float)(n_in - 1) / (float)(n_out - 1) : 0.f;
-  const float fin = (float)o * scale;
-  lo = (int)fin;
-  hi = lo + 1 < n_in - 1 ? lo + 1 : n_in - 1;
-  l = __fmaf_rn((float)o, scale, -(float)lo);   // fin - (float)lo, contracted as in loss.hip
-}
-
-// TF 1.12 ResizeNearestNeighbor(align_corners=True) source index (legacy scaler, roundf)
-__device__ __forceinline__ int nn_src(int o, int n_in, int n_out) {
-  const float scale = n_out > 1 ? (float)(n_in - 1) / (float)(n_out - 1) : (float)n_in / (float)n_out;
-  const int i = (int)roundf((float)o * scale);
-  return i < n_in - 1 ? i : n_in - 1;
-}
 
 // [first, last] of the origins o[0..n) whose window [o[i], o[i] + len) holds p. The origins
 // increase strictly, start at 0, leave no gap and end at canvas - len (checked by the caller), so
@@ -83,89 +70,17 @@ __global__ __launch_bounds__(WIN_THREADS) void window_decisions_kernel(WinArgs a
           float xl;
           lerp_of(f ? a.W - 1 - x : x, a.wl, a.W, xlo, xhi, xl);
           const float* base = a.logits[(iy * a.nx + ix) * per + f] + (size_t)n * image;
-          const float* tl = base + ((size_t)ylo * a.wl + xlo) * a.ld;
-          const float* tr = base + ((size_t)ylo * a.wl + xhi) * a.ld;
-          const float* bl = base + ((size_t)yhi * a.wl + xlo) * a.ld;
-          const float* br = base + ((size_t)yhi * a.wl + xhi) * a.ld;
           float p[CT];
-#pragma unroll
-          for (int c = 0; c < CT; ++c) {
-            // top = tl + (tr - tl) * xl; bot likewise; top + (bot - top) * yl, one fma each
-            const float top = __fmaf_rn(tr[c] - tl[c], xl, tl[c]);
-            const float bot = __fmaf_rn(br[c] - bl[c], xl, bl[c]);
-            p[c] = __fmaf_rn(bot - top, yl, top);
-          }
-          // softmax per head (the same arithmetic as the loss head and the eval kernel)
-          auto softmax = [&](int c0, int nc) {
-            float m = p[c0];
-#pragma unroll
-            for (int c = 1; c < nc; ++c) m = fmaxf(m, p[c0 + c]);
-            float s = 0.f;
-#pragma unroll
-            for (int c = 0; c < nc; ++c) { p[c0 + c] = __expf(p[c0 + c] - m); s += p[c0 + c]; }
-            const float rs = 1.f / s;
-#pragma unroll
-            for (int c = 0; c < nc; ++c) p[c0 + c] = p[c0 + c] * rs;
-          };
-          softmax(0, C1);
-          softmax(C1, C2);
-          softmax(C1 + C2, C3);
-          if (k == 0) {
-#pragma unroll
-            for (int c = 0; c < CT; ++c) acc[c] = p[c];
-          } else {
-#pragma unroll
-            for (int c = 0; c < CT; ++c) acc[c] = __fadd_rn(acc[c], p[c]);   // the rounded p, not an FMA
-          }
+          bilerp<CT>(p, cells_of(base, ylo, yhi, xlo, xhi, a.wl, a.ld), xl, yl);
+          softmax_heads<C1, C2, C3>(p);
+          accumulate<CT>(acc, p, k == 0);
           ++k;
         }
       }
     }
-    if (a.probs) {   // Ho x Wo = Hc x Wc (checked by the caller): id is the canvas pixel
-      const float r = a.rk[k];
-      float* o = a.probs + (size_t)id * CT;
-      if constexpr (CT % 4 == 0) {
-#pragma unroll
-        for (int c = 0; c < CT; c += 4)
-          *reinterpret_cast<float4*>(o + c) = make_float4(acc[c] * r, acc[c + 1] * r,
-                                                          acc[c + 2] * r, acc[c + 3] * r);
-      } else {
-#pragma unroll
-        for (int c = 0; c < CT; ++c) o[c] = acc[c] * r;
-      }
-    }
-    // the eval kernel's decision logic on the sums (a positive common factor changes no order)
-    int d1 = 0;
-    float b1 = acc[0];
-#pragma unroll
-    for (int c = 1; c < C1; ++c) if (acc[c] > b1) { b1 = acc[c]; d1 = c; }
-    int d;
-    if (d1 == t.cid_l1_vehicle) {
-      int b = 0;
-      float bv = acc[C1];
-#pragma unroll
-      for (int c = 1; c < C2; ++c) if (acc[C1 + c] > bv) { bv = acc[C1 + c]; b = c; }
-      d = t.veh_to_common[b];
-    } else if (d1 == t.cid_l1_human) {
-      int b = 0;
-      float bv = acc[C1 + C2];
-#pragma unroll
-      for (int c = 1; c < C3; ++c) if (acc[C1 + C2 + c] > bv) { bv = acc[C1 + C2 + c]; b = c; }
-      d = t.hum_to_common[b];
-    } else {
-      d = t.l1_to_common[d1];
-    }
-    d = a.map[d];   // tf.gather(ocids2ncids, decs)
-    if (a.replace_voids) {
-      // top_k(l1 sums, 2) (stable: equal values keep the lower index first)
-      int d2 = -1;
-      float b2 = 0.f;
-#pragma unroll
-      for (int c = 0; c < C1; ++c)
-        if (c != d1 && (d2 < 0 || acc[c] > b2)) { b2 = acc[c]; d2 = c; }
-      d = d == C1 - 1 ? d2 : d1;
-    }
-    a.out[id] = d;
+    // Ho x Wo = Hc x Wc (checked by the caller): id is the canvas pixel
+    if (a.probs) store_ct<CT>(a.probs + (size_t)id * CT, acc, a.rk[k]);
+    a.out[id] = decide<C1, C2, C3>(acc, t, a.map, a.replace_voids);
   }
 }
 
@@ -203,13 +118,8 @@ hipError_t launch_window_images(const float* in, int n, int Hc, int Wc, int y0, 
 hipError_t launch_window_decisions(const WinArgs& a, const LossTables& t, hipStream_t s) {
   const long total = (long)a.N * a.Ho * a.Wo;
   if (total <= 0) return hipSuccess;
-  long g = (total + WIN_THREADS - 1) / WIN_THREADS;
-  if (g > 8192) g = 8192;
-  if (t.c1 == 14 && t.c2 == 7 && t.c3 == 3)
-    hipLaunchKernelGGL((window_decisions_kernel<14, 7, 3>), dim3((int)g), dim3(WIN_THREADS), 0, s, a, t);
-  else if (t.c1 == 53 && t.c2 == 12 && t.c3 == 5)
-    hipLaunchKernelGGL((window_decisions_kernel<53, 12, 5>), dim3((int)g), dim3(WIN_THREADS), 0, s, a, t);
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
+  const dim3 g((unsigned)std::min((total + WIN_THREADS - 1) / WIN_THREADS, 8192L));
+  return dispatch_heads(t, [&](auto c1, auto c2, auto c3) {
+    hipLaunchKernelGGL((window_decisions_kernel<c1, c2, c3>), g, dim3(WIN_THREADS), 0, s, a, t);
+  });
 }

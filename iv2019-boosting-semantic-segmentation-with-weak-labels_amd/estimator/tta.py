@@ -199,13 +199,18 @@ def attach_predictions(predictions, driver, entries):
             predictions[f'{head}_logits_lowres'] = entries[i][0][..., lo:lo + ci]
             lo += ci
 
-    def materialise():
-        import torch
-        probs = driver.mean_probabilities(entries)
-        out, lo = {}, 0
-        for head, ci in zip(HEADS, driver.widths):
-            out[f'{head}_probabilities'] = probs[..., lo:lo + ci]
-            out[f'{head}_decisions'] = torch.argmax(probs[..., lo:lo + ci], dim=-1).to(torch.int32)
-            lo += ci
-        return out
-    predictions.use_tta(materialise)
+    predictions.use_tta(lambda: materialise(driver, entries))
+
+
+def materialise(driver, entries):
+    """The lazy ``*_probabilities`` (per-head slices of ``driver.mean_probabilities(entries)``) and
+    ``*_decisions`` (their argmax) of a TTADriver or a WindowDriver."""
+    import torch
+    from models.resnet50_extended_model_hierarchical import HEADS
+    probs = driver.mean_probabilities(entries)
+    out, lo = {}, 0
+    for head, ci in zip(HEADS, driver.widths):
+        out[f'{head}_probabilities'] = probs[..., lo:lo + ci]
+        out[f'{head}_decisions'] = torch.argmax(probs[..., lo:lo + ci], dim=-1).to(torch.int32)
+        lo += ci
+    return out

@@ -15,9 +15,9 @@ where they are used.
 """
 from __future__ import annotations
 
+from estimator.tta import HEAD_LAYOUT, materialise
+
 MAX_ENTRIES = 64   # SEG_WIN_MAX_ENTRIES: windows x (1 + flip) of one decision launch
-# seg_cfg.dataset (0 cityscapes, 1 vistas) -> (head widths l1 | l2 vehicle | l2 human, training classes)
-HEAD_LAYOUT = {0: ((14, 7, 3), 20), 1: ((53, 12, 5), 66)}
 
 
 def add_window_arguments(argparser):
@@ -170,15 +170,5 @@ def attach_window_predictions(predictions, driver, entries):
     their per-head argmax, and neither ``*_logits`` nor ``*_logits_lowres`` exist (no single
     forward saw the canvas). Materialising runs the decision head once more over all entries
     (``WindowDriver.mean_probabilities``)."""
-    from models.resnet50_extended_model_hierarchical import HEADS
-
-    def materialise():
-        import torch
-        probs = driver.mean_probabilities(entries)
-        out, lo = {}, 0
-        for head, ci in zip(HEADS, driver.widths):
-            out[f'{head}_probabilities'] = probs[..., lo:lo + ci]
-            out[f'{head}_decisions'] = torch.argmax(probs[..., lo:lo + ci], dim=-1).to(torch.int32)
-            lo += ci
-        return out
-    predictions.use_tta(materialise)   # the same lazy-entry hook; the windows' KeyError is the model's
+    # the same lazy-entry hook; the windows' KeyError is the model's
+    predictions.use_tta(lambda: materialise(driver, entries))

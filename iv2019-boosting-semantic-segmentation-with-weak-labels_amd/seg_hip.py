@@ -343,6 +343,21 @@ class SegContext:
         check(LIB.seg_set_bn_inference(self.h, 1 if on else 0), self.h)
         self.bn_inference = bool(on)
 
+    def _decision_args(self, cid_map, out, mean_probs=None, hw="H, W"):
+        """(batch size, cid_map as a C array) after the checks the decision calls share: ``out`` a
+        contiguous device int32 [N, Ho, Wo], ``mean_probs`` None or a contiguous device float32
+        [N, ``hw``, C]."""
+        import torch
+        n = self.cfg.nb_pp + self.cfg.nb_pb + self.cfg.nb_pi
+        if not (out.dtype == torch.int32 and out.dim() == 3 and out.is_contiguous()
+                and out.shape[0] == n and out.is_cuda):
+            raise ValueError(f"decisions buffer must be a contiguous device int32 [{n}, Ho, Wo]")
+        if mean_probs is not None and not (mean_probs.dtype == torch.float32 and mean_probs.is_cuda
+                                           and mean_probs.is_contiguous() and mean_probs.dim() == 4
+                                           and mean_probs.shape[0] == n):
+            raise ValueError(f"mean_probs must be a contiguous device float32 [{n}, {hw}, C]")
+        return n, (ctypes.c_int32 * len(cid_map))(*[int(v) for v in cid_map])
+
     def predict(self, cid_map, out, replace_voids=False, stream=None, order="eval"):
         """Decisions of the last forward mapped through ``cid_map`` (training -> eval/inference
         cids, -1 = void), optionally void-replaced, nearest-neighbour resized to out's
@@ -352,12 +367,7 @@ class SegContext:
         PREDICT branch, define_estimator_hierarchical.py:227-231)."""
         if order not in ("eval", "predict"):
             raise ValueError(f"order must be 'eval' or 'predict', got {order!r}")
-        m = (ctypes.c_int32 * len(cid_map))(*[int(v) for v in cid_map])
-        import torch
-        n = self.cfg.nb_pp + self.cfg.nb_pb + self.cfg.nb_pi
-        if not (out.dtype == torch.int32 and out.dim() == 3 and out.is_contiguous()
-                and out.shape[0] == n and out.is_cuda):
-            raise ValueError(f"decisions buffer must be a contiguous device int32 [{n}, Ho, Wo]")
+        _, m = self._decision_args(cid_map, out)
         rv = (2 if order == "predict" else 1) if replace_voids else 0
         check(LIB.seg_predict(self.h, m, len(cid_map), rv,
                               int(out.shape[1]), int(out.shape[2]), _ptr(out), _stream(stream)),
@@ -396,10 +406,7 @@ class SegContext:
         optional device f32 [N, H, W, c1 + c2 + c3] for the mean probabilities; needs out's
         size to be the network size. The context's own logits are not read."""
         import torch
-        n = self.cfg.nb_pp + self.cfg.nb_pb + self.cfg.nb_pi
-        if not (out.dtype == torch.int32 and out.dim() == 3 and out.is_contiguous()
-                and out.shape[0] == n and out.is_cuda):
-            raise ValueError(f"decisions buffer must be a contiguous device int32 [{n}, Ho, Wo]")
+        n, m = self._decision_args(cid_map, out, mean_probs)
         if len(entries) > TTA_MAX_ENTRIES:
             raise ValueError(f"{len(entries)} entries: at most {TTA_MAX_ENTRIES} "
                              "(scales x flips) per decision launch")
@@ -411,11 +418,6 @@ class SegContext:
                                  f"[{n}, h_low, w_low, ld], got {tuple(lg.shape)} {lg.dtype}")
             arr[i] = TtaEntry(lg.data_ptr(), int(lg.shape[1]), int(lg.shape[2]), int(lg.shape[3]),
                               int(flip))
-        if mean_probs is not None and not (mean_probs.dtype == torch.float32 and mean_probs.is_cuda
-                                           and mean_probs.is_contiguous() and mean_probs.dim() == 4
-                                           and mean_probs.shape[0] == n):
-            raise ValueError(f"mean_probs must be a contiguous device float32 [{n}, H, W, C]")
-        m = (ctypes.c_int32 * len(cid_map))(*[int(v) for v in cid_map])
         check(LIB.seg_tta_decisions(self.h, arr, len(entries), m, len(cid_map), int(replace_voids),
                                     int(out.shape[1]), int(out.shape[2]), _ptr(mean_probs),
                                     _ptr(out), _stream(stream)), self.h)
@@ -432,10 +434,7 @@ class SegContext:
         [N, Hc, Wc, c1 + c2 + c3]; needs out's size to be the canvas size. The context's own
         logits are not read."""
         import torch
-        n = self.cfg.nb_pp + self.cfg.nb_pb + self.cfg.nb_pi
-        if not (out.dtype == torch.int32 and out.dim() == 3 and out.is_contiguous()
-                and out.shape[0] == n and out.is_cuda):
-            raise ValueError(f"decisions buffer must be a contiguous device int32 [{n}, Ho, Wo]")
+        n, m = self._decision_args(cid_map, out, mean_probs, "Hc, Wc")
         ys, xs = [int(v) for v in ys], [int(v) for v in xs]
         want = len(ys) * len(xs) * (2 if flip else 1)
         if want > WIN_MAX_ENTRIES:
@@ -451,12 +450,7 @@ class SegContext:
                 raise ValueError(f"entry {i}: logits must be a contiguous device float32 "
                                  f"[{n}, h_low, w_low, ld] of the first entry's shape {shape}, "
                                  f"got {tuple(lg.shape)} {lg.dtype}")
-        if mean_probs is not None and not (mean_probs.dtype == torch.float32 and mean_probs.is_cuda
-                                           and mean_probs.is_contiguous() and mean_probs.dim() == 4
-                                           and mean_probs.shape[0] == n):
-            raise ValueError(f"mean_probs must be a contiguous device float32 [{n}, Hc, Wc, C]")
         ptrs = (_VP * want)(*[lg.data_ptr() for lg in entries])
-        m = (ctypes.c_int32 * len(cid_map))(*[int(v) for v in cid_map])
         check(LIB.seg_window_decisions(self.h, ptrs, shape[1], shape[2], shape[3],
                                        (_INT * len(ys))(*ys), len(ys), (_INT * len(xs))(*xs), len(xs),
                                        int(bool(flip)), int(canvas_hw[0]), int(canvas_hw[1]), m,

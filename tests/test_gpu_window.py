@@ -19,8 +19,6 @@ evaluate.py / predict.py flags.
 import argparse
 import ctypes
 import errno
-import importlib.util
-import os
 
 import numpy as np
 import pytest
@@ -28,45 +26,12 @@ import torch
 
 import tta_ref
 import window_ref
+from inference_common import (MAPS, PROBLEM, _realistic_moving_stats, _rel, _script,  # noqa: F401
+                              city_ctx, vistas_ctx)
 
 pytestmark = pytest.mark.gpu
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(REPO, "iv2019-boosting-semantic-segmentation-with-weak-labels_amd")
-PROBLEM = os.path.join(PKG, "problem_definitions", "cityscapes", "problem01.json")
-
-# the maps of tests/test_gpu_tta.py (copied)
-MAPS = {
-    "identity": list(range(19)) + [-1],
-    # merge some classes, ignore others (-1 -> void = max + 1)
-    "merge": [0, 0, 1, 1, 2, -1, 3, 3, 4, 5, 6, 7, 7, 8, 8, 8, 9, 9, 9, -1],
-}
 H, W = window_ref.NET_HW
-
-
-def _rel(a, b):
-    a = np.asarray(a, np.float64)
-    b = np.asarray(b, np.float64)
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
-
-
-def _script(name):
-    spec = importlib.util.spec_from_file_location(f"seg_{name}_window_gpu", os.path.join(PKG, f"{name}.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def _realistic_moving_stats(ctx, images):
-    """Moving statistics = the batch statistics of one training-mode forward (as in
-    tests/test_gpu_tta.py), so that the moving-statistics forward gives logits in the range a
-    trained checkpoint gives."""
-    ctx.set_bn_inference(False)
-    ctx.forward(images)
-    torch.cuda.synchronize()
-    ctx.moving.copy_(ctx.grads[ctx.n_train:ctx.n_train + ctx.n_moving])
-    ctx.params_updated()
-    ctx.set_bn_inference(True)
 
 
 # ---- seg_window_images ---------------------------------------------------------------------
@@ -128,29 +93,6 @@ def test_window_images_rejects_bad_arguments(cuda):
 
 
 # ---- canvas = network size: the bits of seg_predict / seg_full_predictions / seg_tta_decisions
-
-@pytest.fixture(scope="module")
-def city_ctx(cuda):
-    """A 64 x 128 PSP fp32 context after a moving-statistics forward."""
-    from input_pipelines.synthetic import batch
-    from models.initializers import init_params
-    from seg_hip import SegContext
-    ctx = SegContext(pyramid="psp", height=64, width=128, nb_pp=2, dtype="fp32")
-    ctx.load_params(init_params(ctx.param_info, seed=3))
-    _realistic_moving_stats(ctx, torch.as_tensor(batch(99, 2, 0, 0, 64, 128)["images"]).to(cuda))
-    ctx.forward(torch.as_tensor(batch(12, 2, 0, 0, 64, 128)["images"]).to(cuda))
-    yield ctx
-    ctx.close()
-
-
-@pytest.fixture(scope="module")
-def vistas_ctx(cuda):
-    """A 53 | 12 | 5 context of the synthetic logits' network size (its forward is not used)."""
-    from seg_hip import SegContext
-    ctx = SegContext(pyramid="none", height=64, width=128, nb_pp=2, dtype="fp32", dataset="vistas")
-    yield ctx
-    ctx.close()
-
 
 @pytest.mark.parametrize("replace_voids", [False, True])
 @pytest.mark.parametrize("out_hw", [(64, 128), (45, 77), (128, 256)])
