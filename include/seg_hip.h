@@ -302,6 +302,71 @@ int seg_window_decisions(seg_ctx* ctx, const float* const* logits, int h_low, in
                          int replace_voids, int out_h, int out_w,
                          float* mean_probs_out, int32_t* decisions_out, void* stream);
 
+/* mean-field CRF refinement of the probabilities before the argmax (no reference counterpart: its
+ * predict.py stops at the argmax; the semantics are fixed here). A Potts model with a bilateral
+ * (position + colour) kernel plus a spatial kernel over a finite neighbourhood.
+ * Inputs: probs = P, device fp32 [n][H][W][CT], the per-head probabilities (channels l1 | l2
+ *   vehicle | l2 human, CT = c1 + c2 + c3 from ctx's head tables: 14 + 7 + 3 for Cityscapes,
+ *   53 + 12 + 5 for Vistas) -- probs_out of seg_full_predictions, mean_probs_out of
+ *   seg_tta_decisions or of seg_window_decisions; images = I, device fp32 [n][H][W][3], the
+ *   prepared images in [-1, 1) at the same H x W. n, H, W are this call's arguments: H x W is
+ *   whatever size the probabilities have (the network size, or the canvas of sliding windows) and
+ *   need not be ctx's size; only the head tables and the cid-map rules come from ctx.
+ * Parameters (seg_crf_params): iterations T, radius r, dilation d, the weights w_appearance (w_a)
+ *   and w_smoothness (w_s), theta_alpha in pixels, theta_beta in grey levels of the 0..255 image,
+ *   theta_gamma in pixels.
+ * Neighbourhood: offsets o = (dy * d, dx * d) for dy, dx in -r..r without (0, 0), in row-major
+ *   order of (dy, dx): K = (2r + 1)^2 - 1 offsets. A neighbour outside the image contributes
+ *   nothing: no padding value, no renormalisation.
+ * Kernel weight, the same for the three heads, from the image only; for pixel i and neighbour
+ *   j = i + o:
+ *     k_ij  = ga[o] * exp(-(|I_i - I_j|^2) * inv2b) + gs[o]
+ *     ga[o] = (float)(w_a * exp(-|o|^2 / (2 theta_alpha^2)))
+ *     gs[o] = (float)(w_s * exp(-|o|^2 / (2 theta_gamma^2)))
+ *     inv2b = (float)(1 / (2 (theta_beta * 2 / 255)^2))
+ *   ga[o], gs[o] and inv2b are formed on the host in double (|o|^2 = (dy^2 + dx^2) d^2) and
+ *   rounded to float: they are part of the definition, like the resize tables elsewhere. One grey
+ *   level is 2 / 255 in the prepared image. |I_i - I_j|^2 is the sum of the three squared channel
+ *   differences in channel order; exp is the fast exp (__expf).
+ * Iteration: Q^0 = P; for t = 0..T-1 every pixel is updated from Q^t (a parallel update over two
+ *   buffers):
+ *     m_i(c) = sum over o, in offset order, of k_ij * Q^t_j(c)             (fp32 accumulation)
+ *     per head h: M_h = max over the head of m_i; v(c) = P_i(c) * exp(m_i(c) - M_h);
+ *                 Z_h = sum of v in channel order; Q^{t+1}_i(c) = v(c) * (1 / Z_h)
+ *   P_i(c) in v(c) is the unary, the original probability, not Q^t. If Z_h is not >= 1e-30f the
+ *   head keeps P_i for that pixel. In the Potts model this is Q ~ exp(log P + message), written
+ *   without a logarithm.
+ * Decisions on Q^T exactly as seg_tta_decisions forms them on its sums: per-head first-maximum
+ *   argmax -> hierarchical fusion -> cid_map (-1 -> max + 1) -> replace_voids = 1: the stable top-2
+ *   of the l1 values (2, seg_predict's PREDICT order, is not defined here: -EINVAL) ->
+ *   NEAREST_NEIGHBOR align_corners resize from H x W to out_h x out_w. decisions_out: device int32
+ *   [n][out_h][out_w]. probs_out: optional (NULL skips it) device fp32 [n][H][W][CT] = Q^T,
+ *   16-byte aligned, overlapping neither probs nor the workspace.
+ * T = 0: no mean-field launch runs and Q = P exactly: decisions_out is bitwise what
+ *   seg_tta_decisions writes for the single unflipped entry whose mean_probs_out is this P, and
+ *   probs_out, if given, is a copy of P.
+ * seg_crf_workspace: the bytes of the two Q buffers seg_crf_decisions needs when T >= 1 (each
+ *   n * H * W * ct floats rounded up to 16 bytes). The workspace is the caller's; the entry
+ *   neither allocates, frees nor synchronises.
+ * -EINVAL with a seg_last_error text naming the function and the parameter, and no launch, for:
+ *   iterations outside 0..32; radius outside 1..5; dilation outside 1..4; a weight < 0; a theta
+ *   <= 0; any non-finite parameter; a null ctx, probs, images, p, cid_map or decisions_out; a null
+ *   or too small workspace when T >= 1; probs, probs_out or the workspace not 16-byte aligned; n,
+ *   H, W or an output size < 1; replace_voids outside 0..1; a cid map of the wrong length or with
+ *   an entry < -1. */
+typedef struct seg_crf_params {
+  int iterations, radius, dilation;
+  float w_appearance, w_smoothness;
+  float theta_alpha, theta_beta, theta_gamma;
+} seg_crf_params;
+int seg_crf_workspace(int n, int H, int W, int ct, int64_t* bytes);
+int seg_crf_decisions(seg_ctx* ctx, const float* probs, const float* images,
+                      int n, int H, int W, const seg_crf_params* p,
+                      void* workspace, int64_t workspace_bytes,
+                      const int32_t* cid_map, int n_map, int replace_voids,
+                      int out_h, int out_w,
+                      float* probs_out, int32_t* decisions_out, void* stream);
+
 /* input preprocessing (input_cityscapes.py:66-96,190-209), after the host
  * decodes TFRecord -> tf.train.Example -> PNG (input_pipelines/tfrecords.py):
  * seg_prepare_images: raw uint8 [n][src_h][src_w][3] -> convert_image_dtype -> bilinear

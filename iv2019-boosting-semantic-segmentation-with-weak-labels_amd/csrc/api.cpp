@@ -355,6 +355,114 @@ int seg_window_decisions(seg_ctx* c, const float* const* logits, int h_low, int 
   return 0;
 }
 
+// one Q buffer of the mean-field iteration, rounded up to the 16-byte alignment the kernels ask
+static int64_t crf_buffer_bytes(int n, int H, int W, int ct) {
+  return ((int64_t)n * H * W * ct * (int64_t)sizeof(float) + 15) / 16 * 16;
+}
+
+int seg_crf_workspace(int n, int H, int W, int ct, int64_t* bytes) {
+  if (!bytes || n < 1 || H < 1 || W < 1 || ct < 1)
+    return set_err(nullptr, -EINVAL, "seg_crf_workspace: bad arguments (n %d, H %d, W %d, ct %d%s)",
+                   n, H, W, ct, bytes ? "" : ", null bytes");
+  *bytes = 2 * crf_buffer_bytes(n, H, W, ct);
+  return 0;
+}
+
+int seg_crf_decisions(seg_ctx* c, const float* probs, const float* images, int n, int H, int W,
+                      const seg_crf_params* p, void* workspace, int64_t workspace_bytes,
+                      const int32_t* cid_map, int n_map, int replace_voids, int out_h, int out_w,
+                      float* probs_out, int32_t* decisions_out, void* stream) {
+  const char* who = "seg_crf_decisions";
+  if (!c) return set_err(nullptr, -EINVAL, "%s: null ctx", who);
+  std::string* err = &c->err;
+  if (!probs) return set_err(err, -EINVAL, "%s: null probs", who);
+  if (!images) return set_err(err, -EINVAL, "%s: null images", who);
+  if (!p) return set_err(err, -EINVAL, "%s: null params (seg_crf_params)", who);
+  if (!cid_map) return set_err(err, -EINVAL, "%s: null cid_map", who);
+  if (!decisions_out) return set_err(err, -EINVAL, "%s: null decisions_out", who);
+  if (n < 1 || H < 1 || W < 1)
+    return set_err(err, -EINVAL, "%s: bad size n = %d, H = %d, W = %d", who, n, H, W);
+  if (p->iterations < 0 || p->iterations > CRF_MAX_ITERATIONS)
+    return set_err(err, -EINVAL, "%s: iterations = %d (0..%d)", who, p->iterations, CRF_MAX_ITERATIONS);
+  if (p->radius < 1 || p->radius > CRF_MAX_RADIUS)
+    return set_err(err, -EINVAL, "%s: radius = %d (1..%d)", who, p->radius, CRF_MAX_RADIUS);
+  if (p->dilation < 1 || p->dilation > CRF_MAX_DILATION)
+    return set_err(err, -EINVAL, "%s: dilation = %d (1..%d)", who, p->dilation, CRF_MAX_DILATION);
+  const struct { const char* name; float v; bool weight; } fl[] = {
+      {"w_appearance", p->w_appearance, true}, {"w_smoothness", p->w_smoothness, true},
+      {"theta_alpha", p->theta_alpha, false},  {"theta_beta", p->theta_beta, false},
+      {"theta_gamma", p->theta_gamma, false}};
+  for (const auto& f : fl) {
+    if (!std::isfinite(f.v)) return set_err(err, -EINVAL, "%s: %s is not finite", who, f.name);
+    if (f.weight ? f.v < 0.f : f.v <= 0.f)
+      return set_err(err, -EINVAL, "%s: %s = %g (must be %s 0)", who, f.name, (double)f.v,
+                     f.weight ? ">=" : ">");
+  }
+  const LossTables& t = c->tables;
+  const int ct = t.c1 + t.c2 + t.c3;
+  if (replace_voids == 2)
+    return set_err(err, -EINVAL, "%s: replace_voids = 2 (the PREDICT order on resized "
+                   "probabilities) is not defined for refined probabilities; use 1", who);
+  if (replace_voids < 0 || replace_voids > 1)
+    return set_err(err, -EINVAL, "%s: replace_voids = %d (0 or 1)", who, replace_voids);
+  if (n_map != t.n_pp)
+    return set_err(err, -EINVAL, "%s: cid_map has %d entries, the model has %d training classes",
+                   who, n_map, t.n_pp);
+  if (out_h < 1 || out_w < 1)
+    return set_err(err, -EINVAL, "%s: bad output size out_h x out_w = %dx%d", who, out_h, out_w);
+  if (reinterpret_cast<uintptr_t>(probs) & 15)
+    return set_err(err, -EINVAL, "%s: probs must be 16-byte aligned", who);
+  if (reinterpret_cast<uintptr_t>(probs_out) & 15)
+    return set_err(err, -EINVAL, "%s: probs_out must be 16-byte aligned", who);
+  const int T = p->iterations;
+  const int64_t buf = crf_buffer_bytes(n, H, W, ct);
+  if (T >= 1) {
+    if (!workspace) return set_err(err, -EINVAL, "%s: null workspace with iterations = %d", who, T);
+    if (reinterpret_cast<uintptr_t>(workspace) & 15)
+      return set_err(err, -EINVAL, "%s: workspace must be 16-byte aligned", who);
+    if (workspace_bytes < 2 * buf)
+      return set_err(err, -EINVAL, "%s: workspace of %lld bytes, %lld needed (seg_crf_workspace)",
+                     who, (long long)workspace_bytes, (long long)(2 * buf));
+  }
+  CrfDecideArgs da{};
+  if (int r = normalise_cid_map(c, who, cid_map, n_map, da.map)) return r;
+
+  hipStream_t s = (hipStream_t)stream;
+  const float* q = probs;   // Q^0 = P
+  if (T >= 1) {
+    CrfStepArgs a{};
+    a.p = probs; a.img = images; a.N = n; a.H = H; a.W = W;
+    a.r = p->radius; a.d = p->dilation;
+    const double sb = (double)p->theta_beta * 2.0 / 255.0;   // one grey level of the prepared image
+    a.inv2b = (float)(1.0 / (2.0 * sb * sb));
+    int o = 0;
+    for (int dy = -a.r; dy <= a.r; ++dy)
+      for (int dx = -a.r; dx <= a.r; ++dx, ++o) {
+        if (!dy && !dx) continue;   // the centre is no offset: both tables keep 0 there
+        const double d2 = ((double)dy * dy + (double)dx * dx) * a.d * a.d;
+        a.ga[o] = (float)((double)p->w_appearance *
+                          std::exp(-d2 / (2.0 * (double)p->theta_alpha * (double)p->theta_alpha)));
+        a.gs[o] = (float)((double)p->w_smoothness *
+                          std::exp(-d2 / (2.0 * (double)p->theta_gamma * (double)p->theta_gamma)));
+      }
+    float* ws[2] = {static_cast<float*>(workspace),
+                    reinterpret_cast<float*>(static_cast<char*>(workspace) + buf)};
+    for (int it = 0; it < T; ++it) {
+      a.q = q;
+      a.out = (it == T - 1 && probs_out) ? probs_out : ws[it & 1];
+      HIPCALL(c, launch_crf_step(a, t, s));
+      q = a.out;
+    }
+  } else if (probs_out) {
+    HIPCALL(c, hipMemcpyAsync(probs_out, probs, (size_t)n * H * W * ct * sizeof(float),
+                              hipMemcpyDeviceToDevice, s));
+  }
+  da.q = q; da.N = n; da.H = H; da.W = W; da.Ho = out_h; da.Wo = out_w;
+  da.replace_voids = replace_voids; da.n_map = n_map; da.out = decisions_out;
+  HIPCALL(c, launch_crf_decisions(da, t, s));
+  return 0;
+}
+
 int seg_backward(seg_ctx* c, void* stream) {
   NEED_BOUND(c);
   Step S{c, (hipStream_t)stream, c->dt};

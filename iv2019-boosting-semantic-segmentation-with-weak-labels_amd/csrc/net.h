@@ -20,6 +20,7 @@
 #include "input.h"
 #include "augment.h"
 #include "conv.h"
+#include "crf.h"
 #include "decide.h"
 #include "deconv.h"
 #include "gn.h"

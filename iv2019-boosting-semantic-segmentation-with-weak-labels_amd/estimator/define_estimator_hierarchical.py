@@ -146,8 +146,11 @@ def _eval_spec(predictions, labels, config, params, proimages=None):
     With params.tta_scales / params.tta_flip the decisions come from the probabilities averaged
     over the scaled / mirrored forwards instead (estimator/tta.py, seg_tta_decisions); with
     params.window_canvas from the probabilities averaged over the windows of the canvas that
-    proimages then is (estimator/windows.py, seg_window_decisions)."""
+    proimages then is (estimator/windows.py, seg_window_decisions). With params.crf_iterations > 0
+    the probabilities of whichever of the three paths is active are refined by the mean-field CRF
+    on proimages before the argmax (estimator/crf.py, seg_crf_decisions)."""
     import torch
+    from estimator.crf import driver_for_crf, refine_decisions
     from estimator.tta import attach_predictions, driver_for
     from estimator.windows import attach_window_predictions, driver_for_windows
     from utils.utils import _replacevoids
@@ -161,7 +164,10 @@ def _eval_spec(predictions, labels, config, params, proimages=None):
     replace = bool(getattr(params, 'replace_voids', False))
     win = driver_for_windows(ctx, config, params, ModeKeys.EVAL)
     tta = None if win is not None else driver_for(ctx, config, params, ModeKeys.EVAL)
-    if win is not None:   # --window_canvas: proimages is the canvas, every window a forward
+    crf = driver_for_crf(ctx, params)
+    if crf is not None:   # --crf_iterations: the active path's probabilities, refined
+        refine_decisions(crf, predictions, proimages, tcids2ecids, decs, replace, win, tta)
+    elif win is not None:   # --window_canvas: proimages is the canvas, every window a forward
         attach_window_predictions(predictions, win,
                                   win.decisions(proimages, tcids2ecids, decs, replace))
     elif tta is None:
@@ -189,8 +195,11 @@ def _predict_spec(predictions, features, params, config=None):
     from the averaged probabilities (estimator/tta.py); --replace_voids then replaces at the
     network size before the resize (mode 1 of seg_predict: the resize-first order is not defined
     for averaged probabilities). params.window_canvas: the same from the windows of the canvas
-    (estimator/windows.py)."""
+    (estimator/windows.py). params.crf_iterations > 0: the probabilities of the active path are
+    refined by the mean-field CRF on the prepared images first (estimator/crf.py);
+    --replace_voids then also replaces before the resize (mode 1)."""
     import torch
+    from estimator.crf import driver_for_crf, refine_decisions
     from estimator.tta import attach_predictions, driver_for
     from estimator.windows import attach_window_predictions, driver_for_windows
     ctx = predictions['_context']
@@ -204,7 +213,11 @@ def _predict_spec(predictions, features, params, config=None):
     decs = torch.empty((n,) + tuple(size), dtype=torch.int32, device=img.device)
     win = driver_for_windows(ctx, config, params, ModeKeys.PREDICT)
     tta = None if win is not None else driver_for(ctx, config, params, ModeKeys.PREDICT)
-    if win is not None:   # --window_canvas: img is the canvas, every window a forward
+    crf = driver_for_crf(ctx, params)
+    if crf is not None:   # --crf_iterations: the active path's probabilities, refined
+        refine_decisions(crf, predictions, img, list(range(params.output_Nclasses)), decs, replace,
+                         win, tta)
+    elif win is not None:   # --window_canvas: img is the canvas, every window a forward
         attach_window_predictions(predictions, win,
                                   win.decisions(img, list(range(params.output_Nclasses)), decs, replace))
     elif tta is None:

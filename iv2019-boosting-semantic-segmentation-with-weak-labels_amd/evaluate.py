@@ -42,6 +42,7 @@ def _add_extra_args(args):
 
 
 def build_arguments():
+    from estimator.crf import add_crf_arguments
     from estimator.tta import add_tta_arguments
     from estimator.windows import add_window_arguments
     ssargs = SemanticSegmentationArguments(mode=ModeKeys.EVAL)
@@ -53,6 +54,7 @@ def build_arguments():
     ssargs.argparser.add_argument('--tfrecords_path', type=str, default=None)
     add_tta_arguments(ssargs.argparser)
     add_window_arguments(ssargs.argparser)
+    add_crf_arguments(ssargs.argparser)
     return ssargs
 
 
@@ -62,6 +64,8 @@ def main(argv, max_steps=None):
     _add_extra_args(args)
     from estimator.windows import window_settings
     window_settings(args)   # refuses --tta_scales with --window_canvas before anything is built
+    from estimator.crf import crf_settings
+    crf_settings(args)   # refuses a bad --crf_* value the same way
     system = SemanticSegmentation({'eval': tfrecord_eval_fn if args.tfrecords_path else eval_fn},
                                   model_fn, args)
     all_metrics = system.evaluate(max_steps=max_steps)

@@ -163,6 +163,8 @@ class Predictions(MutableMapping):
         self._forward_id = getattr(ctx, 'forward_count', 0)
         self._c = (53, 12, 5) if dataset == 'vistas' else (14, 7, 3)
         self._tta = None   # set by use_tta
+        self._refined = None   # set by use_refined
+        self._refined_entries = None
         self._windows = canvas is not None   # sliding windows: (n, Hc, Wc), no forward has run
         if self._windows:
             self._shape = tuple(int(v) for v in canvas)
@@ -206,7 +208,18 @@ class Predictions(MutableMapping):
         mean probabilities at the canvas size."""
         self._tta = materialise
 
+    def use_refined(self, entries):
+        """CRF refinement (estimator/crf.py): ``entries()`` returns the ``*_probabilities`` /
+        ``*_decisions`` of the refined probabilities Q^T, which then stand in for the model's (or
+        the averaged) ones; the ``*_logits`` entries are untouched."""
+        self._refined = entries
+        self._refined_entries = None
+
     def __getitem__(self, k):
+        if self._refined is not None and k in LAZY_KEYS and not k.endswith('_logits'):
+            if self._refined_entries is None:
+                self._refined_entries = self._refined()
+            return self._refined_entries[k]
         if self._windows and k not in self._store and (
                 k in LAZY_KEYS or k.endswith('_logits_lowres')):
             if k.endswith('_logits') or k.endswith('_logits_lowres') or self._tta is None:
@@ -244,7 +257,7 @@ class Predictions(MutableMapping):
 
     def materialised(self):
         """The entries computed so far (no launch): a plain dict."""
-        return dict(self._store)
+        return dict(self._store, **(self._refined_entries or {}))
 
 
 def add_model_arguments(argparser):

@@ -73,6 +73,7 @@ def _add_predict_arguments(argparser):
 
 
 def build_arguments():
+    from estimator.crf import add_crf_arguments
     from estimator.tta import add_tta_arguments
     from estimator.windows import add_window_arguments
     ssargs = SemanticSegmentationArguments(mode=ModeKeys.PREDICT)
@@ -80,6 +81,7 @@ def build_arguments():
     _add_predict_arguments(ssargs.argparser)
     add_tta_arguments(ssargs.argparser)
     add_window_arguments(ssargs.argparser)
+    add_crf_arguments(ssargs.argparser)
     return ssargs
 
 
@@ -90,6 +92,8 @@ def main(argv, max_steps=None):
     s.batch_norm_decay = 1.0
     from estimator.windows import window_settings
     window_settings(s)   # refuses --tta_scales with --window_canvas before anything is built
+    from estimator.crf import crf_settings
+    crf_settings(s)   # refuses a bad --crf_* value the same way
     if s.plotting or s.plotting_overlapped:
         raise NotImplementedError('live plotting is not built; use the --export_* flags')
     if s.export_lids_images or s.export_color_decisions or s.export_overlapped_color_decisions:

@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = [
     "seg_augment_profile_blur", "seg_set_bootstrap", "seg_op_bootstrap_threshold",
     "seg_resize_images", "seg_tta_decisions",
     "seg_window_images", "seg_window_decisions",
+    "seg_crf_workspace", "seg_crf_decisions",
 ]
 
 # int (*seg_allreduce_fn)(void* user, float* buf, int64_t n, void* stream)
@@ -98,6 +99,14 @@ WIN_MAX_ENTRIES = 64   # SEG_WIN_MAX_ENTRIES
 class TtaEntry(ctypes.Structure):
     """seg_tta_entry (include/seg_hip.h); logits is a device address"""
     _fields_ = [("logits", _VP), ("h_low", _INT), ("w_low", _INT), ("ld", _INT), ("flip", _INT)]
+
+
+class CrfParams(ctypes.Structure):
+    """seg_crf_params (include/seg_hip.h)"""
+    _fields_ = [("iterations", _INT), ("radius", _INT), ("dilation", _INT),
+                ("w_appearance", ctypes.c_float), ("w_smoothness", ctypes.c_float),
+                ("theta_alpha", ctypes.c_float), ("theta_beta", ctypes.c_float),
+                ("theta_gamma", ctypes.c_float)]
 
 
 def _load():
@@ -195,6 +204,9 @@ def _load():
         "seg_window_decisions": (ip, [vp, ctypes.POINTER(vp), ip, ip, ip, ctypes.POINTER(ip), ip,
                                       ctypes.POINTER(ip), ip, ip, ip, ip,
                                       ctypes.POINTER(ctypes.c_int32), ip, ip, ip, ip, vp, vp, vp]),
+        "seg_crf_workspace": (ip, [ip, ip, ip, ip, ctypes.POINTER(i64)]),
+        "seg_crf_decisions": (ip, [vp, vp, vp, ip, ip, ip, ctypes.POINTER(CrfParams), vp, i64,
+                                   ctypes.POINTER(ctypes.c_int32), ip, ip, ip, ip, vp, vp, vp]),
     }
     override = "SEG_HIP_LIB" in os.environ   # A/B builds of older commits may lack new entries
     for name, (res, args) in sig.items():
@@ -213,6 +225,13 @@ def check(rc: int, ctx=None):
     if rc != 0:
         msg = LIB.seg_last_error(ctx)
         raise RuntimeError(f"libseg_hip error {rc}: {msg.decode() if msg else ''}")
+
+
+def crf_workspace_bytes(n: int, H: int, W: int, ct: int) -> int:
+    """seg_crf_workspace: bytes of the two Q buffers of ``SegContext.crf_decisions``."""
+    b = ctypes.c_int64()
+    check(LIB.seg_crf_workspace(int(n), int(H), int(W), int(ct), ctypes.byref(b)))
+    return b.value
 
 
 def _ptr(t) -> Optional[int]:
@@ -457,6 +476,40 @@ class SegContext:
                                        len(cid_map), int(replace_voids), int(out.shape[1]),
                                        int(out.shape[2]), _ptr(mean_probs), _ptr(out),
                                        _stream(stream)), self.h)
+
+    def crf_decisions(self, probs, images, crf, cid_map, out, replace_voids=False, workspace=None,
+                      probs_out=None, stream=None):
+        """seg_crf_decisions: decisions from ``probs`` (contiguous device f32 [n, H, W, c1 + c2 +
+        c3], per-head probabilities) after ``crf.iterations`` mean-field steps conditioned on
+        ``images`` (contiguous device f32 [n, H, W, 3], the prepared batch at the same size).
+        ``crf``: a ``CrfParams``. ``cid_map`` / ``out`` / ``replace_voids`` as in
+        ``tta_decisions``; the nearest resize to out's size starts from H x W, the size of
+        ``probs``, whatever the context's own size is. ``workspace``: a contiguous device buffer of
+        at least ``crf_workspace_bytes(n, H, W, ct)`` bytes (needed when iterations >= 1; the
+        caller owns it). ``probs_out``: optional device f32 of probs' shape for the refined
+        probabilities Q^T."""
+        import torch
+        ok = lambda t, c: (t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.dim() == 4
+                           and (c is None or t.shape[3] == c))
+        if not ok(probs, None):
+            raise ValueError("probs must be a contiguous device float32 [n, H, W, c1 + c2 + c3]")
+        n, H, W, ct = (int(v) for v in probs.shape)
+        if not (ok(images, 3) and tuple(images.shape[:3]) == (n, H, W)):
+            raise ValueError(f"images must be a contiguous device float32 [{n}, {H}, {W}, 3], got "
+                             f"{tuple(images.shape)} {images.dtype}")
+        if not (out.dtype == torch.int32 and out.dim() == 3 and out.is_contiguous()
+                and out.shape[0] == n and out.is_cuda):
+            raise ValueError(f"decisions buffer must be a contiguous device int32 [{n}, Ho, Wo]")
+        if probs_out is not None and not (ok(probs_out, ct) and probs_out.shape == probs.shape):
+            raise ValueError(f"probs_out must be a contiguous device float32 {tuple(probs.shape)}")
+        if workspace is not None and not (workspace.is_cuda and workspace.is_contiguous()):
+            raise ValueError("workspace must be a contiguous device buffer")
+        m = (ctypes.c_int32 * len(cid_map))(*[int(v) for v in cid_map])
+        ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+        check(LIB.seg_crf_decisions(self.h, _ptr(probs), _ptr(images), n, H, W, ctypes.byref(crf),
+                                    _ptr(workspace), ws_bytes, m, len(cid_map), int(replace_voids),
+                                    int(out.shape[1]), int(out.shape[2]), _ptr(probs_out), _ptr(out),
+                                    _stream(stream)), self.h)
 
     def backward(self, stream=None):
         check(LIB.seg_backward(self.h, _stream(stream)), self.h)
