@@ -82,7 +82,7 @@ BnBwdArgs bn_bwd_op_args(const seg_bn_bwd_args* p) {
   a.dyhat = p->dyhat; a.lddyhat = p->lddyhat;
   a.dzscale = p->dzscale; a.dshift = p->dshift;
   a.beta = p->beta; a.cs_part = p->cs_part;
-  a.part = p->part; a.rb = bn_bwd_rowblocks(a.M, a.C);
+  a.part = p->part; a.rb = bn_bwd_rowblocks(a.M);
   return a;
 }
 
@@ -376,7 +376,7 @@ int seg_op_conv_wgrad_cfg(int dtype, const void* dy, int N, int Ho, int Wo, int 
 
 int seg_op_bn_rowblocks(int64_t M, int C) {
   if (M < 1 || C < 1) return set_err(nullptr, -EINVAL, "seg_op_bn_rowblocks: bad arguments");
-  return bn_bwd_rowblocks((long)M, C);
+  return bn_bwd_rowblocks((long)M);
 }
 
 int seg_op_bn_stats_finalize(const float* part, int64_t M, int C, int tile_rows, const float* gamma,
@@ -386,7 +386,7 @@ int seg_op_bn_stats_finalize(const float* part, int64_t M, int C, int tile_rows,
     return set_err(nullptr, -EINVAL, "seg_op_bn_stats_finalize: bad arguments");
   BnState st{};
   st.mean = mean; st.invstd = invstd; st.scale = scale; st.var_unb = var_unb;
-  hipError_t e = launch_bn_stats_finalize(part, (long)M, C, tile_rows, nullptr, gamma, st,
+  hipError_t e = launch_bn_stats_finalize(part, (long)M, C, tile_rows, gamma, st,
                                           (hipStream_t)stream, pack);
   return e == hipSuccess ? 0 : hip_fail(nullptr, e, "seg_op_bn_stats_finalize");
 }
@@ -412,7 +412,7 @@ int seg_op_bn_apply(int dtype, int out_f32, const seg_bn_apply_args* p, void* st
   a.Ho = p->Ho; a.Wo = p->Wo; a.Hr = p->Hr; a.Wr = p->Wr;
   a.y2 = p->y2; a.ldy2 = p->ldy2; a.mean2 = p->mean2; a.scale2 = p->scale2; a.beta2 = p->beta2;
   a.out = p->out; a.ldo = p->ldo; a.mask = p->mask;
-  if (a.mask && (!a.relu || !bn_apply_is_v8(a)))
+  if (a.mask && (!a.relu || !bn_apply_plan(a).wide))
     return set_err(nullptr, -EINVAL, "seg_op_bn_apply: ReLU bits exist on the 8-wide path only, "
                    "with relu");
   hipError_t e = launch_bn_apply(dt_of(dtype), out_f32, a, (hipStream_t)stream);
@@ -429,8 +429,8 @@ int seg_op_bn_backward(int dtype, int dz_f32, int frozen, int reduce_only, const
   if (p->dyhat && p->lddyhat < p->C) return set_err(nullptr, -EINVAL, "%s: bad arguments", who);
   BnBwdArgs a = bn_bwd_op_args(p);
   a.reduce_dyhat = reduce_only && p->dyhat ? 1 : 0;
-  const char* why = bn_bwd_reduce_refusal(dt_of(dtype), a);
-  if (!why && !reduce_only) why = bn_bwd_apply_refusal(a);
+  const char* why = bn_bwd_reduce_plan(dt_of(dtype), a).refusal;
+  if (!why && !reduce_only) why = bn_bwd_apply_plan(a).refusal;
   if (why) return set_err(nullptr, -EINVAL, "%s: %s", who, why);
   hipStream_t s = (hipStream_t)stream;
   BnState st{};
@@ -464,10 +464,8 @@ int seg_op_bn_backward_dual(int dtype, int frozen, int second_only, const seg_bn
   BnState st{}, st2{};
   st.sdy = p->sdy; st.sdyx = p->sdyx;
   st2.sdy = q->sdy; st2.sdyx = q->sdyx;
+  if (const char* why = bn_bwd_dual_plan(a).refusal) return set_err(nullptr, -EINVAL, "%s: %s", who, why);
   hipError_t e = launch_bn_bwd_reduce_dual(dt_of(dtype), a, s);
-  if (e == hipErrorInvalidValue)
-    return set_err(nullptr, -EINVAL, "%s: the dual kernels take 8-wide layouts, the bits, and no z / "
-                   "dzscale / dyhat", who);
   if (e == hipSuccess) e = launch_bn_bwd_finalize(a.part, a.rb, a.M, a.C, st, p->dgamma, p->dbeta, s, frozen);
   if (e == hipSuccess) e = launch_bn_bwd_finalize(a2.part, a2.rb, a.M, a.C, st2, q->dgamma, q->dbeta, s, frozen);
   if (e == hipSuccess)

@@ -63,27 +63,91 @@ struct BnBwdArgs {
   float* part2;
 };
 
+// ---- kernel selection: what a launch's arguments choose, asked by the launchers and their callers
+// The 8-channel streaming kernels' layout rule: C and every row stride in use (or-ed into lds)
+// a multiple of 8, p16 (the first 16-byte access) aligned. Otherwise the scalar kernels run.
+inline bool bn_wide(int C, int lds, const void* p16) {
+  return ((C | lds) & 7) == 0 && (uintptr_t)p16 % 16 == 0;
+}
+
+enum { RES_NONE = 0, RES_PLAIN = 1, RES_SUB = 2, RES_BN2 = 3 };
+struct BnApplyPlan {
+  bool wide;   // the 8-channel kernels (the only ones that write ReLU bits)
+  int res;     // RES_*
+  bool relu;
+};
+inline BnApplyPlan bn_apply_plan(const BnApplyArgs& a) {
+  BnApplyPlan p;
+  p.wide = bn_wide(a.C, a.ldy | a.ldo | (a.res ? a.ldres : 0) | (a.y2 ? a.ldy2 : 0), a.out);
+  p.res = a.y2 ? RES_BN2 : (a.res ? (a.rs > 1 ? RES_SUB : RES_PLAIN) : RES_NONE);
+  p.relu = a.relu != 0;
+  return p;
+}
+
+// The backward's variants (the table: DESIGN.md, batch norm). The values are the 8-wide kernels'
+// HZ and HS template arguments.
+enum { BN_GATE_NONE = 0, BN_GATE_Z = 1, BN_GATE_BITS = 2 };
+enum { BN_TERM_NONE = 0, BN_TERM_DZSCALE = 1, BN_TERM_DSHIFT = 2 };
+struct BnBwdPlan {
+  bool wide;
+  int gate;              // BN_GATE_*: the bits win over z
+  int term;              // BN_TERM_*: the per-channel term of dz
+  bool dyhat;            // this launch stores the gated gradient
+  bool colsum;           // the reduce also forms cs_part
+  const char* refusal;   // nullptr: launch; else why the launcher returns hipErrorInvalidValue
+};
+inline BnBwdPlan bn_bwd_plan_base(const BnBwdArgs& a) {
+  BnBwdPlan p{};
+  p.wide = bn_wide(a.C, a.lddz | a.ldy | (a.z ? a.ldz : 0) | (a.dy ? a.lddy : 0) | (a.dyhat ? a.lddyhat : 0), a.dz);
+  p.gate = a.mask ? BN_GATE_BITS : (a.z ? BN_GATE_Z : BN_GATE_NONE);
+  if (a.mask && !p.wide) p.refusal = "ReLU bits exist on the 8-wide path only";
+  return p;
+}
+inline BnBwdPlan bn_bwd_reduce_plan(int dtype, const BnBwdArgs& a) {
+  BnBwdPlan p = bn_bwd_plan_base(a);
+  p.dyhat = a.reduce_dyhat && a.dyhat;   // reduce_dyhat moves the store out of the apply
+  p.colsum = a.cs_part != nullptr;
+  // with the bits the reduce drops dzscale (group norm's gamma: the apply alone carries it)
+  p.term = a.dshift ? BN_TERM_DSHIFT : (a.dzscale && !a.mask ? BN_TERM_DZSCALE : BN_TERM_NONE);
+  if (p.refusal) return p;
+  if ((a.dshift || p.dyhat) && (!a.mask || a.dzscale || !p.wide))
+    p.refusal = "dshift / a reduce-side dyhat need the ReLU bits, the 8-wide path and no dzscale";
+  else if (p.colsum && (!a.dshift || p.dyhat || !a.beta || !seg_half(dtype)))
+    p.refusal = "cs_part needs dshift, beta, a 16-bit type and no reduce-side dyhat";
+  return p;
+}
+inline BnBwdPlan bn_bwd_apply_plan(const BnBwdArgs& a) {
+  BnBwdPlan p = bn_bwd_plan_base(a);
+  p.dyhat = a.dyhat != nullptr;
+  p.term = a.dshift ? BN_TERM_DSHIFT : (a.dzscale ? BN_TERM_DZSCALE : BN_TERM_NONE);
+  if (!p.refusal && a.dshift && (!a.mask || a.dzscale || a.dyhat || !p.wide))
+    p.refusal = "dshift in the apply needs the ReLU bits, the 8-wide path, no dzscale and no dyhat";
+  return p;
+}
+// the dual launches (reduce and apply alike): two layers of 8-wide layouts gated by the bits
+inline BnBwdPlan bn_bwd_dual_plan(const BnBwdArgs& a) {
+  BnBwdPlan p{};
+  p.wide = bn_wide(a.C, a.lddz | a.ldy | a.ldy2 | a.lddy | a.lddy2, a.dz);
+  p.gate = BN_GATE_BITS;
+  if (!a.mask || a.z || a.dzscale || a.dyhat || !p.wide)
+    p.refusal = "the dual kernels take 8-wide layouts, the bits, and no z / dzscale / dyhat";
+  return p;
+}
+
 // pack (nullable, [2C]): also writes [mean | E[x^2]] for a cross-replica exchange
 hipError_t launch_bn_stats_finalize(const float* tile_part, long M, int C, int tile_rows,
-                                    float* scratch, const float* gamma, BnState st,
-                                    hipStream_t s, float* pack = nullptr);
+                                    const float* gamma, BnState st, hipStream_t s,
+                                    float* pack = nullptr);
 // cross-replica BN: the replica-summed pack -> global mean / biased variance in st
 hipError_t launch_bn_sync_unpack(const float* pack, int C, float inv_world, const float* gamma,
                                  BnState st, hipStream_t s);
-// inference mode, every layer in one launch (one workgroup per job)
+// inference mode (st from the moving statistics), every layer in one launch (one workgroup per job)
 struct BnInferJob { const float* mov_mean; const float* mov_var; const float* gamma; BnState st; int C; };
 hipError_t launch_bn_infer_finalize_all(const BnInferJob* jobs, int n, hipStream_t s);
-// inference mode: st from the moving statistics (no batch statistics)
-hipError_t launch_bn_infer_finalize(const float* mov_mean, const float* mov_var, int C,
-                                    const float* gamma, BnState st, hipStream_t s);
 hipError_t launch_bn_apply(int dtype, int out_f32, const BnApplyArgs& a, hipStream_t s);
-// does this launch take the 8-channel streaming kernels (the only ones that write ReLU bits)?
-bool bn_apply_is_v8(const BnApplyArgs& a);
-int bn_bwd_rowblocks(long M, int C);
-// why launch_bn_bwd_reduce / launch_bn_bwd_apply return hipErrorInvalidValue for these arguments
-// without launching (nullptr: they launch); the launchers test exactly these
-const char* bn_bwd_reduce_refusal(int dtype, const BnBwdArgs& a);
-const char* bn_bwd_apply_refusal(const BnBwdArgs& a);
+int bn_bwd_rowblocks(long M);
+// the backward launchers map their plan to a kernel: hipErrorInvalidValue, nothing launched,
+// where the plan refuses
 hipError_t launch_bn_bwd_reduce(int dtype, int dz_f32, const BnBwdArgs& a, hipStream_t s);
 // frozen: is_training=False statistics (moving averages): the batch means do not depend on
 // the input, so sdy = sdyx = 0 and dy = gamma * invstd * dyhat (FusedBatchNormGrad, inference)

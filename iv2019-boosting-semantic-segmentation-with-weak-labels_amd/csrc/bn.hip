@@ -3,8 +3,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-// (non-temporal stores for the apply kernels' outputs measured no faster)
-#define BN_STORE8(T, p, v) Vec8<T>::store(p, v)
+// (non-temporal stores for the apply kernels' outputs measured no faster than Vec8's)
 
 namespace {
 
@@ -153,18 +152,6 @@ __global__ void bn_sync_unpack_kernel(const float* __restrict__ pack, int C, flo
 // inference-mode BN (tf.contrib.layers.batch_norm is_training=False, i.e.
 // batch_norm_accumulate_statistics unset; hierarchical.py:306-307): the moving statistics
 // take the place of the batch statistics in the same apply kernel
-__global__ void bn_infer_finalize_kernel(const float* __restrict__ mov_mean,
-                                         const float* __restrict__ mov_var, int C,
-                                         const float* gamma, BnState st) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  const float inv = rsqrtf(mov_var[c] + SEG_BN_EPS);
-  st.mean[c] = mov_mean[c];
-  st.invstd[c] = inv;
-  st.scale[c] = gamma[c] * inv;
-  st.var_unb[c] = mov_var[c];
-}
-
 __global__ void bn_infer_finalize_all_kernel(const BnInferJob* __restrict__ jobs) {
   const BnInferJob j = jobs[blockIdx.x];
   for (int c = threadIdx.x; c < j.C; c += blockDim.x) {
@@ -177,33 +164,22 @@ __global__ void bn_infer_finalize_all_kernel(const BnInferJob* __restrict__ jobs
 }
 
 // ---- forward apply ---------------------------------------------------------------------
-template <typename T, typename TO, int VEC, typename IDX>
+// The scalar kernels: any layout, one element per thread pass (the narrow logits layers:
+// C = 14 / 7 / 3).
+template <typename T, typename TO, typename IDX>
 __device__ __forceinline__ void bn_apply_body(const BnApplyArgs& a) {
-  const int cg_n = a.C / VEC;
-  const IDX total = (IDX)(a.M * cg_n);
+  const IDX total = (IDX)(a.M * a.C);
   const T* Y = (const T*)a.y;
   const T* RES = (const T*)a.res;
   const T* Y2 = (const T*)a.y2;
   TO* O = (TO*)a.out;
   for (IDX it = (IDX)blockIdx.x * blockDim.x + threadIdx.x; it < total;
        it += (IDX)gridDim.x * blockDim.x) {
-    const IDX m = it / (IDX)cg_n;
-    const int c0 = (int)(it - m * cg_n) * VEC;
-    float v[VEC];
-    if constexpr (VEC == 8) {
-      Vec8<T>::load(Y + (size_t)m * a.ldy + c0, v);
-    } else {
-      v[0] = ldf(Y + (size_t)m * a.ldy + c0);
-    }
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) v[e] = (v[e] - a.mean[c0 + e]) * a.scale[c0 + e] + a.beta[c0 + e];
+    const IDX m = it / (IDX)a.C;
+    const int c = (int)(it - m * a.C);
+    float v = (ldf(Y + (size_t)m * a.ldy + c) - a.mean[c]) * a.scale[c] + a.beta[c];
     if (Y2) {
-      float u[VEC];
-      if constexpr (VEC == 8) Vec8<T>::load(Y2 + (size_t)m * a.ldy2 + c0, u);
-      else u[0] = ldf(Y2 + (size_t)m * a.ldy2 + c0);
-#pragma unroll
-      for (int e = 0; e < VEC; ++e)
-        v[e] = ((u[e] - a.mean2[c0 + e]) * a.scale2[c0 + e] + a.beta2[c0 + e]) + v[e];
+      v = ((ldf(Y2 + (size_t)m * a.ldy2 + c) - a.mean2[c]) * a.scale2[c] + a.beta2[c]) + v;
     } else if (RES) {
       size_t rm = (size_t)m;
       if (a.rs > 1) {
@@ -213,35 +189,32 @@ __device__ __forceinline__ void bn_apply_body(const BnApplyArgs& a) {
         long n = t / a.Ho;
         rm = (size_t)((n * a.Hr + ho * a.rs) * a.Wr + wo * a.rs);
       }
-      float u[VEC];
-      if constexpr (VEC == 8) Vec8<T>::load(RES + rm * a.ldres + c0, u);
-      else u[0] = ldf(RES + rm * a.ldres + c0);
-#pragma unroll
-      for (int e = 0; e < VEC; ++e) v[e] = u[e] + v[e];  // shortcut + residual
+      v = ldf(RES + rm * a.ldres + c) + v;  // shortcut + residual
     }
-    if (a.relu) {
-#pragma unroll
-      for (int e = 0; e < VEC; ++e) v[e] = fmaxf(v[e], 0.f);
-    }
-    if constexpr (VEC == 8) Vec8<TO>::store(O + (size_t)m * a.ldo + c0, v);
-    else stf(O + (size_t)m * a.ldo + c0, v[0]);
+    if (a.relu) v = fmaxf(v, 0.f);
+    stf(O + (size_t)m * a.ldo + c, v);
   }
 }
 
-// generic-layout apply (the narrow logits layers: C = 14 / 7 / 3): 32-bit element indices when
-// they fit (round 5: the 64-bit division per element was most of these launches' ~10 us)
-template <typename T, typename TO, int VEC>
+// 32-bit element indices when they fit (round 5: the 64-bit division per element was most of
+// these launches' ~10 us)
+template <typename T, typename TO>
 __global__ void bn_apply_kernel(BnApplyArgs a) {
-  if (a.M * (a.C / VEC) < (1L << 31)) bn_apply_body<T, TO, VEC, unsigned>(a);
-  else bn_apply_body<T, TO, VEC, long>(a);
+  if (a.M * a.C < (1L << 31)) bn_apply_body<T, TO, unsigned>(a);
+  else bn_apply_body<T, TO, long>(a);
 }
 
 // ---- backward reduce: per row block partial sums of dyhat and dyhat*xhat -----------------
-// block: 256 threads = RL row lanes x CGB channel groups (VEC channels each)
-template <typename T, typename TZ, int VEC>
+// The two scalar backward kernels keep their values in one-element arrays indexed by e < ONE:
+// written over plain floats the compiler schedules them differently (the same arithmetic, other
+// machine code), and these kernels are pinned instruction for instruction.
+constexpr int ONE = 1;
+
+// block: 256 threads = row lanes x channels
+template <typename T, typename TZ>
 __global__ void bn_bwd_reduce_kernel(BnBwdArgs a) {
-  const int cg_n = a.C / VEC;
-  const int cgb = cg_n < 256 ? cg_n : 256;       // channel groups per block pass
+  const int cg_n = a.C / ONE;
+  const int cgb = cg_n < 256 ? cg_n : 256;       // channels per block pass
   const int rl_n = 256 / cgb;                     // row lanes
   const int tcg = threadIdx.x % cgb, trl = threadIdx.x / cgb;
   const long rows_per = (a.M + a.rb - 1) / a.rb;
@@ -250,37 +223,31 @@ __global__ void bn_bwd_reduce_kernel(BnBwdArgs a) {
   const TZ* DZ = (const TZ*)a.dz;
   const TZ* Z = (const TZ*)a.z;
   const T* Y = (const T*)a.y;
-  __shared__ float sh[2][256 * VEC];
+  __shared__ float sh[2][256];
   for (int base = 0; base < cg_n; base += cgb) {
     const int cg = base + tcg;
     const bool act = cg < cg_n;
-    const int c0 = act ? cg * VEC : 0;
-    float s1[VEC], s2[VEC], mu[VEC], inv[VEC];
+    const int c0 = act ? cg * ONE : 0;
+    float s1[ONE], s2[ONE], mu[ONE], inv[ONE];
 #pragma unroll
-    for (int e = 0; e < VEC; ++e) { s1[e] = 0.f; s2[e] = 0.f; mu[e] = a.mean[c0 + e]; inv[e] = a.invstd[c0 + e]; }
+    for (int e = 0; e < ONE; ++e) { s1[e] = 0.f; s2[e] = 0.f; mu[e] = a.mean[c0 + e]; inv[e] = a.invstd[c0 + e]; }
     if (act && trl < rl_n) {
       for (long m = r0 + trl; m < r1; m += rl_n) {
-        float dz[VEC], y[VEC];
-        if constexpr (VEC == 8) {
-          Vec8<TZ>::load(DZ + (size_t)m * a.lddz + c0, dz);
-          Vec8<T>::load(Y + (size_t)m * a.ldy + c0, y);
-        } else {
-          dz[0] = ldf(DZ + (size_t)m * a.lddz + c0);
-          y[0] = ldf(Y + (size_t)m * a.ldy + c0);
-        }
+        float dz[ONE], y[ONE];
+        dz[0] = ldf(DZ + (size_t)m * a.lddz + c0);
+        y[0] = ldf(Y + (size_t)m * a.ldy + c0);
         if (Z) {
-          float z[VEC];
-          if constexpr (VEC == 8) Vec8<TZ>::load(Z + (size_t)m * a.ldz + c0, z);
-          else z[0] = ldf(Z + (size_t)m * a.ldz + c0);
+          float z[ONE];
+          z[0] = ldf(Z + (size_t)m * a.ldz + c0);
 #pragma unroll
-          for (int e = 0; e < VEC; ++e) dz[e] = z[e] > 0.f ? dz[e] : 0.f;
+          for (int e = 0; e < ONE; ++e) dz[e] = z[e] > 0.f ? dz[e] : 0.f;
         }
         if (a.dzscale) {
 #pragma unroll
-          for (int e = 0; e < VEC; ++e) dz[e] *= a.dzscale[c0 + e];
+          for (int e = 0; e < ONE; ++e) dz[e] *= a.dzscale[c0 + e];
         }
 #pragma unroll
-        for (int e = 0; e < VEC; ++e) {
+        for (int e = 0; e < ONE; ++e) {
           s1[e] += dz[e];
           s2[e] += dz[e] * ((y[e] - mu[e]) * inv[e]);
         }
@@ -289,19 +256,19 @@ __global__ void bn_bwd_reduce_kernel(BnBwdArgs a) {
     // reduce over row lanes through LDS (fixed order)
     __syncthreads();
 #pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-      sh[0][threadIdx.x * VEC + e] = s1[e];
-      sh[1][threadIdx.x * VEC + e] = s2[e];
+    for (int e = 0; e < ONE; ++e) {
+      sh[0][threadIdx.x * ONE + e] = s1[e];
+      sh[1][threadIdx.x * ONE + e] = s2[e];
     }
     __syncthreads();
     if (act && trl == 0) {
       for (int r = 1; r < rl_n; ++r) {
         int t = r * cgb + tcg;
 #pragma unroll
-        for (int e = 0; e < VEC; ++e) { s1[e] += sh[0][t * VEC + e]; s2[e] += sh[1][t * VEC + e]; }
+        for (int e = 0; e < ONE; ++e) { s1[e] += sh[0][t * ONE + e]; s2[e] += sh[1][t * ONE + e]; }
       }
 #pragma unroll
-      for (int e = 0; e < VEC; ++e) {
+      for (int e = 0; e < ONE; ++e) {
         float* o = a.part + 2 * ((size_t)blockIdx.x * a.C + c0 + e);
         o[0] = s1[e];
         o[1] = s2[e];
@@ -310,10 +277,9 @@ __global__ void bn_bwd_reduce_kernel(BnBwdArgs a) {
   }
 }
 
-template <typename T, typename TZ, int VEC, typename IDX>
+template <typename T, typename TZ, typename IDX>
 __device__ __forceinline__ void bn_bwd_apply_body(const BnBwdArgs& a) {
-  const int cg_n = a.C / VEC;
-  const IDX total = (IDX)(a.M * cg_n);
+  const IDX total = (IDX)(a.M * a.C);
   const TZ* DZ = (const TZ*)a.dz;
   const TZ* Z = (const TZ*)a.z;
   const T* Y = (const T*)a.y;
@@ -321,47 +287,37 @@ __device__ __forceinline__ void bn_bwd_apply_body(const BnBwdArgs& a) {
   T* DH = (T*)a.dyhat;
   for (IDX it = (IDX)blockIdx.x * blockDim.x + threadIdx.x; it < total;
        it += (IDX)gridDim.x * blockDim.x) {
-    const IDX m = it / (IDX)cg_n;
-    const int c0 = (int)(it - m * cg_n) * VEC;
-    float dz[VEC], y[VEC];
-    if constexpr (VEC == 8) {
-      Vec8<TZ>::load(DZ + (size_t)m * a.lddz + c0, dz);
-      Vec8<T>::load(Y + (size_t)m * a.ldy + c0, y);
-    } else {
-      dz[0] = ldf(DZ + (size_t)m * a.lddz + c0);
-      y[0] = ldf(Y + (size_t)m * a.ldy + c0);
-    }
+    const IDX m = it / (IDX)a.C;
+    const int c0 = (int)(it - m * a.C);
+    float dz[ONE], y[ONE];
+    dz[0] = ldf(DZ + (size_t)m * a.lddz + c0);
+    y[0] = ldf(Y + (size_t)m * a.ldy + c0);
     if (Z) {
-      float z[VEC];
-      if constexpr (VEC == 8) Vec8<TZ>::load(Z + (size_t)m * a.ldz + c0, z);
-      else z[0] = ldf(Z + (size_t)m * a.ldz + c0);
+      float z[ONE];
+      z[0] = ldf(Z + (size_t)m * a.ldz + c0);
 #pragma unroll
-      for (int e = 0; e < VEC; ++e) dz[e] = z[e] > 0.f ? dz[e] : 0.f;
+      for (int e = 0; e < ONE; ++e) dz[e] = z[e] > 0.f ? dz[e] : 0.f;
     }
-    if (DH) {   // the masked gradient before any per-channel factor
-      if constexpr (VEC == 8) Vec8<T>::store(DH + (size_t)m * a.lddyhat + c0, dz);
-      else stf(DH + (size_t)m * a.lddyhat + c0, dz[0]);
-    }
+    if (DH) stf(DH + (size_t)m * a.lddyhat + c0, dz[0]);   // the masked gradient before any per-channel factor
     if (a.dzscale) {
 #pragma unroll
-      for (int e = 0; e < VEC; ++e) dz[e] *= a.dzscale[c0 + e];
+      for (int e = 0; e < ONE; ++e) dz[e] *= a.dzscale[c0 + e];
     }
-    float o[VEC];
+    float o[ONE];
 #pragma unroll
-    for (int e = 0; e < VEC; ++e) {
+    for (int e = 0; e < ONE; ++e) {
       const int c = c0 + e;
       float xh = (y[e] - a.mean[c]) * a.invstd[c];
       o[e] = a.scale[c] * (dz[e] - a.sdy[c] - xh * a.sdyx[c]);
     }
-    if constexpr (VEC == 8) Vec8<T>::store(DY + (size_t)m * a.lddy + c0, o);
-    else stf(DY + (size_t)m * a.lddy + c0, o[0]);
+    stf(DY + (size_t)m * a.lddy + c0, o[0]);
   }
 }
 
-template <typename T, typename TZ, int VEC>
+template <typename T, typename TZ>
 __global__ void bn_bwd_apply_kernel(BnBwdArgs a) {
-  if (a.M * (a.C / VEC) < (1L << 31)) bn_bwd_apply_body<T, TZ, VEC, unsigned>(a);
-  else bn_bwd_apply_body<T, TZ, VEC, long>(a);
+  if (a.M * a.C < (1L << 31)) bn_bwd_apply_body<T, TZ, unsigned>(a);
+  else bn_bwd_apply_body<T, TZ, long>(a);
 }
 
 // ---- 8-channel streaming kernels (C % 8 == 0): thread -> fixed channel group ------------
@@ -394,7 +350,6 @@ __device__ __forceinline__ void ld8(const float* p, int c0, float* o) {
 // Row loops are split into full groups (U valid rows: no bounds tests, all loads issued
 // before any use) and one guarded tail group, and every optional input is a template
 // parameter, so the compiler emits straight-line load batches.
-enum { RES_NONE = 0, RES_PLAIN = 1, RES_SUB = 2, RES_BN2 = 3 };
 
 template <typename T, typename TO, int RES, int RELU>
 __global__ __launch_bounds__(256) void bn_apply8_kernel(BnApplyArgs a) {
@@ -440,7 +395,7 @@ __global__ __launch_bounds__(256) void bn_apply8_kernel(BnApplyArgs a) {
         else if constexpr (RES != RES_NONE) x = u[k][e] + x;
         o[e] = RELU ? fmaxf(x, 0.f) : x;
       }
-      BN_STORE8(TO, O + (size_t)(base + k * L.rpp) * a.ldo, o);
+      Vec8<TO>::store(O + (size_t)(base + k * L.rpp) * a.ldo, o);
       if (RELU && a.mask) {   // bits of the value as stored (> 0 after rounding)
         uint32_t bits = 0;
 #pragma unroll
@@ -482,7 +437,8 @@ template <> struct Raw8<float> {
   }
 };
 
-// masked incoming gradient for n rows (dz * [z > 0] * dzscale) and the matching y rows
+// masked incoming gradient for n rows ((dz [+ dshift]) * [z > 0] [* dzscale]) and the matching y
+// rows. The apply passes HS == 1 as 0: it stores dyhat before it multiplies by dzscale itself.
 template <typename T, typename TZ, int HZ, int HS, bool FULL>
 __device__ __forceinline__ void bwd_load(const BnBwdArgs& a, int c0, long base, int rpp, int nrows,
                                          float (&dz)[BN_U][8], float (&y)[BN_U][8]) {
@@ -575,7 +531,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce8_kernel(BnBwdArgs a) {
         T* DH = (T*)a.dyhat + c0;
 #pragma unroll
         for (int k = 0; k < BN_U; ++k)
-          if (decltype(full)::value || k < nrows) BN_STORE8(T, DH + (size_t)(base + k * L.rpp) * a.lddyhat, dz[k]);
+          if (decltype(full)::value || k < nrows) Vec8<T>::store(DH + (size_t)(base + k * L.rpp) * a.lddyhat, dz[k]);
       }
 #pragma unroll
       for (int k = 0; k < BN_U; ++k)
@@ -653,7 +609,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply8_kernel(BnBwdArgs a) {
       if (k >= nrows) continue;
       const size_t m = (size_t)(base + k * L.rpp);
       // dyhat: the masked gradient before the per-channel factor (group norm's gamma)
-      if constexpr (HD) BN_STORE8(T, DH + m * a.lddyhat, dz[k]);
+      if constexpr (HD) Vec8<T>::store(DH + m * a.lddyhat, dz[k]);
       if constexpr (HS == 1) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) dz[k][e] *= ds[e];
@@ -664,7 +620,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply8_kernel(BnBwdArgs a) {
         const float xh = (y[k][e] - mu[e]) * inv[e];
         o[e] = sc[e] * (dz[k][e] - sdy[e] - xh * sdyx[e]);
       }
-      BN_STORE8(T, DY + m * a.lddy, o);
+      Vec8<T>::store(DY + m * a.lddy, o);
     }
   };
   long base = (long)blockIdx.x * step + L.rl;
@@ -796,18 +752,10 @@ __global__ __launch_bounds__(256) void bn_bwd_apply8_dual_kernel(BnBwdArgs a) {
         o[e] = sc[e] * (d - sdy[e] - ((y[e] - mu[e]) * inv[e]) * sdyx[e]);
         o2[e] = sc2[e] * (d - sdy2[e] - ((y2[e] - mu2[e]) * inv2[e]) * sdyx2[e]);
       }
-      BN_STORE8(T, DY + (size_t)m * a.lddy, o);
-      BN_STORE8(T, DY2 + (size_t)m * a.lddy2, o2);
+      Vec8<T>::store(DY + (size_t)m * a.lddy, o);
+      Vec8<T>::store(DY2 + (size_t)m * a.lddy2, o2);
     }
   }
-}
-
-dim3 grid8(long M, int C) {
-  const int cg_n = C / 8;
-  const int rpp = cg_n >= 256 ? 1 : 256 / cg_n;
-  long g = (M + (long)rpp * BN_U - 1) / ((long)rpp * BN_U);
-  if (g > 2048) g = 2048;
-  return dim3((unsigned)(g < 1 ? 1 : g), cg_n > 256 ? (unsigned)ceil_div(cg_n, 256) : 1u);
 }
 
 __global__ void moving_update_kernel(float* mm, float* mv, const float* bm, const float* bv, int n,
@@ -819,123 +767,32 @@ __global__ void moving_update_kernel(float* mm, float* mv, const float* bm, cons
   mv[i] -= (1.f - decay) * (mv[i] - bv[i]);
 }
 
+// ---- grids ------------------------------------------------------------------------------
+// the 8-wide kernels' blockIdx.y: channel groups past a block's 256 threads (row_lane)
+unsigned blocks_y(int C) { return C / 8 > 256 ? (unsigned)ceil_div(C / 8, 256) : 1u; }
+
+// the streaming (apply) kernels: BN_U rows per thread and pass, at most 2,048 blocks of rows
+dim3 grid8(long M, int C) {
+  const int cg_n = C / 8;
+  const int rpp = cg_n >= 256 ? 1 : 256 / cg_n;
+  long g = (M + (long)rpp * BN_U - 1) / ((long)rpp * BN_U);
+  if (g > 2048) g = 2048;
+  return dim3((unsigned)(g < 1 ? 1 : g), blocks_y(C));
+}
+
 int grid_for(long items) {
   long g = (items + 255) / 256;
   return (int)(g < 4096 ? (g < 1 ? 1 : g) : 4096);
 }
 
-bool apply_v8(const BnApplyArgs& a) {
-  return (a.C % 8 == 0) && (a.ldy % 8 == 0) && (a.ldo % 8 == 0) &&
-         (!a.res || a.ldres % 8 == 0) && (!a.y2 || a.ldy2 % 8 == 0) &&
-         (((uintptr_t)a.out) % 16 == 0);
-}
-
-template <typename T, typename TO>
-hipError_t apply_t(const BnApplyArgs& a, hipStream_t s) {
-  if (apply_v8(a)) {
-    const int res = a.y2 ? RES_BN2 : (a.res ? (a.rs > 1 ? RES_SUB : RES_PLAIN) : RES_NONE);
-    const dim3 g = grid8(a.M, a.C);
-#define BN_APPLY_CASE(R)                                                                      \
-    if (res == R) {                                                                           \
-      if (a.relu) hipLaunchKernelGGL((bn_apply8_kernel<T, TO, R, 1>), g, dim3(256), 0, s, a); \
-      else hipLaunchKernelGGL((bn_apply8_kernel<T, TO, R, 0>), g, dim3(256), 0, s, a);        \
-    }
-    BN_APPLY_CASE(RES_NONE) BN_APPLY_CASE(RES_PLAIN) BN_APPLY_CASE(RES_SUB) BN_APPLY_CASE(RES_BN2)
-#undef BN_APPLY_CASE
-  }
-  else hipLaunchKernelGGL((bn_apply_kernel<T, TO, 1>), dim3(grid_for(a.M * a.C)), dim3(256), 0, s, a);
-  return hipGetLastError();
-}
-
-bool bwd_v8(const BnBwdArgs& a) {
-  return (a.C % 8 == 0) && (a.lddz % 8 == 0) && (a.ldy % 8 == 0) && (!a.z || a.ldz % 8 == 0) &&
-         (!a.dy || a.lddy % 8 == 0) && (!a.dyhat || a.lddyhat % 8 == 0) &&
-         ((uintptr_t)a.dz % 16 == 0);
-}
-
-template <typename T, typename TZ>
-hipError_t bwd_reduce_t(const BnBwdArgs& a, hipStream_t s) {
-  if (bn_bwd_reduce_refusal(sizeof(T) == 2 ? SEG_BF16 : SEG_F32, a)) return hipErrorInvalidValue;
-  const bool rdh = a.reduce_dyhat && a.dyhat;
-  if (bwd_v8(a)) {
-    const int cg_n = a.C / 8;
-    const dim3 g(a.rb, cg_n > 256 ? ceil_div(cg_n, 256) : 1);
-    if (a.cs_part) hipLaunchKernelGGL((bn_bwd_reduce8_kernel<T, TZ, 2, 2, 0, 1>), g, dim3(256), 0, s, a);
-    else if (a.mask && a.dshift && rdh) hipLaunchKernelGGL((bn_bwd_reduce8_kernel<T, TZ, 2, 2, 1>), g, dim3(256), 0, s, a);
-    else if (a.mask && a.dshift) hipLaunchKernelGGL((bn_bwd_reduce8_kernel<T, TZ, 2, 2, 0>), g, dim3(256), 0, s, a);
-    else if (a.mask && rdh) hipLaunchKernelGGL((bn_bwd_reduce8_kernel<T, TZ, 2, 0, 1>), g, dim3(256), 0, s, a);
-    else if (a.mask) hipLaunchKernelGGL((bn_bwd_reduce8_kernel<T, TZ, 2, 0>), g, dim3(256), 0, s, a);
-    else if (a.z && a.dzscale) hipLaunchKernelGGL((bn_bwd_reduce8_kernel<T, TZ, 1, 1>), g, dim3(256), 0, s, a);
-    else if (a.z) hipLaunchKernelGGL((bn_bwd_reduce8_kernel<T, TZ, 1, 0>), g, dim3(256), 0, s, a);
-    else if (a.dzscale) hipLaunchKernelGGL((bn_bwd_reduce8_kernel<T, TZ, 0, 1>), g, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((bn_bwd_reduce8_kernel<T, TZ, 0, 0>), g, dim3(256), 0, s, a);
-  }
-  else hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, TZ, 1>), dim3(a.rb), dim3(256), 0, s, a);
-  return hipGetLastError();
-}
-
-template <typename T, typename TZ>
-hipError_t bwd_apply_t(const BnBwdArgs& a, hipStream_t s) {
-  if (bn_bwd_apply_refusal(a)) return hipErrorInvalidValue;
-  if (bwd_v8(a)) {
-    const dim3 g = grid8(a.M, a.C);
-    const int key = (a.z ? 4 : 0) | (a.dzscale ? 2 : 0) | (a.dyhat ? 1 : 0);
-    if (a.dshift) {
-      hipLaunchKernelGGL((bn_bwd_apply8_kernel<T, TZ, 2, 2, 0>), g, dim3(256), 0, s, a);
-      return hipGetLastError();
-    }
-    if (a.mask) {   // ReLU bits; dzscale with them only under group norm (gamma)
-      if (a.dzscale) {
-        if (a.dyhat) hipLaunchKernelGGL((bn_bwd_apply8_kernel<T, TZ, 2, 1, 1>), g, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((bn_bwd_apply8_kernel<T, TZ, 2, 1, 0>), g, dim3(256), 0, s, a);
-      } else if (a.dyhat) {
-        hipLaunchKernelGGL((bn_bwd_apply8_kernel<T, TZ, 2, 0, 1>), g, dim3(256), 0, s, a);
-      } else {
-        hipLaunchKernelGGL((bn_bwd_apply8_kernel<T, TZ, 2, 0, 0>), g, dim3(256), 0, s, a);
-      }
-      return hipGetLastError();
-    }
-    switch (key) {
-      case 0: hipLaunchKernelGGL((bn_bwd_apply8_kernel<T, TZ, 0, 0, 0>), g, dim3(256), 0, s, a); break;
-      case 1: hipLaunchKernelGGL((bn_bwd_apply8_kernel<T, TZ, 0, 0, 1>), g, dim3(256), 0, s, a); break;
-      case 2: hipLaunchKernelGGL((bn_bwd_apply8_kernel<T, TZ, 0, 1, 0>), g, dim3(256), 0, s, a); break;
-      case 3: hipLaunchKernelGGL((bn_bwd_apply8_kernel<T, TZ, 0, 1, 1>), g, dim3(256), 0, s, a); break;
-      case 4: hipLaunchKernelGGL((bn_bwd_apply8_kernel<T, TZ, 1, 0, 0>), g, dim3(256), 0, s, a); break;
-      case 5: hipLaunchKernelGGL((bn_bwd_apply8_kernel<T, TZ, 1, 0, 1>), g, dim3(256), 0, s, a); break;
-      case 6: hipLaunchKernelGGL((bn_bwd_apply8_kernel<T, TZ, 1, 1, 0>), g, dim3(256), 0, s, a); break;
-      default: hipLaunchKernelGGL((bn_bwd_apply8_kernel<T, TZ, 1, 1, 1>), g, dim3(256), 0, s, a); break;
-    }
-  }
-  else hipLaunchKernelGGL((bn_bwd_apply_kernel<T, TZ, 1>), dim3(grid_for(a.M * a.C)), dim3(256), 0, s, a);
-  return hipGetLastError();
-}
+// a backward plan's variant as one switch key; the launchers list the tuples that exist
+constexpr int bwd_key(int hz, int hs, int hd, int cs) { return ((hz * 3 + hs) * 2 + hd) * 2 + cs; }
 
 }  // namespace
 
-bool bn_apply_is_v8(const BnApplyArgs& a) { return apply_v8(a); }
-
-const char* bn_bwd_reduce_refusal(int dtype, const BnBwdArgs& a) {
-  if (a.mask && !bwd_v8(a)) return "ReLU bits exist on the 8-wide path only";
-  const bool rdh = a.reduce_dyhat && a.dyhat;
-  if ((a.dshift || rdh) && (!a.mask || a.dzscale || !bwd_v8(a)))
-    return "dshift / a reduce-side dyhat need the ReLU bits, the 8-wide path and no dzscale";
-  if (a.cs_part && (!a.dshift || rdh || !a.beta || !seg_half(dtype)))
-    return "cs_part needs dshift, beta, a 16-bit type and no reduce-side dyhat";
-  return nullptr;
-}
-
-const char* bn_bwd_apply_refusal(const BnBwdArgs& a) {
-  if (a.mask && !bwd_v8(a)) return "ReLU bits exist on the 8-wide path only";
-  if (a.dshift && (!a.mask || a.dzscale || a.dyhat || !bwd_v8(a)))
-    return "dshift in the apply needs the ReLU bits, the 8-wide path, no dzscale and no dyhat";
-  return nullptr;
-}
-
 hipError_t launch_bn_stats_finalize(const float* tile_part, long M, int C, int tile_rows,
-                                    float* scratch, const float* gamma, BnState st,
-                                    hipStream_t s, float* pack) {
+                                    const float* gamma, BnState st, hipStream_t s, float* pack) {
   int ntiles = ceil_div(M, tile_rows);
-  (void)scratch;
   hipLaunchKernelGGL(bn_stats_final_kernel, dim3(ceil_div(C, FIN_CH)), dim3(FIN_CH * FIN_LANES), 0,
                      s, tile_part, M, C, tile_rows, ntiles, gamma, st, pack);
   return hipGetLastError();
@@ -954,44 +811,58 @@ hipError_t launch_bn_infer_finalize_all(const BnInferJob* jobs, int n, hipStream
   return hipGetLastError();
 }
 
-hipError_t launch_bn_infer_finalize(const float* mov_mean, const float* mov_var, int C,
-                                    const float* gamma, BnState st, hipStream_t s) {
-  hipLaunchKernelGGL(bn_infer_finalize_kernel, dim3(ceil_div(C, 64)), dim3(64), 0, s, mov_mean,
-                     mov_var, C, gamma, st);
-  return hipGetLastError();
-}
-
 hipError_t launch_bn_apply(int dtype, int out_f32, const BnApplyArgs& a, hipStream_t s) {
-  if (dtype == SEG_BF16) {
-    if (out_f32) return apply_t<bf16_t, float>(a, s);
-    return apply_t<bf16_t, bf16_t>(a, s);
-  }
-  if (dtype == SEG_F16) {
-    if (out_f32) return apply_t<f16_t, float>(a, s);
-    return apply_t<f16_t, f16_t>(a, s);
-  }
-  return apply_t<float, float>(a, s);
+  const BnApplyPlan p = bn_apply_plan(a);
+  return dispatch_dtype2(dtype, out_f32, [&](auto t, auto to) {
+    using T = TAG_T(t);
+    using TO = TAG_T(to);
+    if (!p.wide) {
+      hipLaunchKernelGGL((bn_apply_kernel<T, TO>), dim3(grid_for(a.M * a.C)), dim3(256), 0, s, a);
+      return;
+    }
+    const dim3 g = grid8(a.M, a.C);
+    switch (p.res * 2 + p.relu) {
+#define BN_CASE(RES, RELU) \
+  case RES * 2 + RELU: hipLaunchKernelGGL((bn_apply8_kernel<T, TO, RES, RELU>), g, dim3(256), 0, s, a); break;
+      BN_CASE(RES_NONE, 0) BN_CASE(RES_NONE, 1) BN_CASE(RES_PLAIN, 0) BN_CASE(RES_PLAIN, 1)
+      BN_CASE(RES_SUB, 0) BN_CASE(RES_SUB, 1) BN_CASE(RES_BN2, 0) BN_CASE(RES_BN2, 1)
+#undef BN_CASE
+    }
+  });
 }
 
-int bn_bwd_rowblocks(long M, int C) {
+int bn_bwd_rowblocks(long M) {
   // ~1024 blocks, each >= 64 rows
   const long cap = 1024;
   long rb = (M + 63) / 64;
   if (rb > cap) rb = cap;
-  (void)C;
   return (int)(rb < 1 ? 1 : rb);
 }
 
+// The backward launchers: the plan (bn.h) refuses or names a row of the table (batch
+// norm); a tuple that is no row launches nothing.
 hipError_t launch_bn_bwd_reduce(int dtype, int dz_f32, const BnBwdArgs& a, hipStream_t s) {
-  if (dtype == SEG_BF16) {
-    if (dz_f32) return bwd_reduce_t<bf16_t, float>(a, s);
-    return bwd_reduce_t<bf16_t, bf16_t>(a, s);
-  }
-  if (dtype == SEG_F16) {
-    if (dz_f32) return bwd_reduce_t<f16_t, float>(a, s);
-    return bwd_reduce_t<f16_t, f16_t>(a, s);
-  }
-  return bwd_reduce_t<float, float>(a, s);
+  const BnBwdPlan p = bn_bwd_reduce_plan(dtype, a);
+  if (p.refusal) return hipErrorInvalidValue;
+  bool row = true;
+  const hipError_t e = dispatch_dtype2(dtype, dz_f32, [&](auto t, auto tz) {
+    using T = TAG_T(t);
+    using TZ = TAG_T(tz);
+    if (!p.wide) {   // z and dzscale by their pointers
+      hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, TZ>), dim3(a.rb), dim3(256), 0, s, a);
+      return;
+    }
+    const dim3 g(a.rb, blocks_y(a.C));
+    switch (bwd_key(p.gate, p.term, p.dyhat, p.colsum)) {
+#define BN_CASE(HZ, HS, HD, CS) \
+  case bwd_key(HZ, HS, HD, CS): hipLaunchKernelGGL((bn_bwd_reduce8_kernel<T, TZ, HZ, HS, HD, CS>), g, dim3(256), 0, s, a); break;
+      BN_CASE(2, 2, 0, 1) BN_CASE(2, 2, 1, 0) BN_CASE(2, 2, 0, 0) BN_CASE(2, 0, 1, 0) BN_CASE(2, 0, 0, 0)
+      BN_CASE(1, 1, 0, 0) BN_CASE(1, 0, 0, 0) BN_CASE(0, 1, 0, 0) BN_CASE(0, 0, 0, 0)
+#undef BN_CASE
+      default: row = false;
+    }
+  });
+  return row ? e : hipErrorInvalidValue;
 }
 
 hipError_t launch_bn_bwd_finalize(const float* part, int rb, long M, int C, BnState st,
@@ -1002,53 +873,42 @@ hipError_t launch_bn_bwd_finalize(const float* part, int rb, long M, int C, BnSt
 }
 
 hipError_t launch_bn_bwd_apply(int dtype, int dz_f32, const BnBwdArgs& a, hipStream_t s) {
-  if (dtype == SEG_BF16) {
-    if (dz_f32) return bwd_apply_t<bf16_t, float>(a, s);
-    return bwd_apply_t<bf16_t, bf16_t>(a, s);
-  }
-  if (dtype == SEG_F16) {
-    if (dz_f32) return bwd_apply_t<f16_t, float>(a, s);
-    return bwd_apply_t<f16_t, f16_t>(a, s);
-  }
-  return bwd_apply_t<float, float>(a, s);
-}
-
-template <typename T>
-bool dual_ok(const BnBwdArgs& a) {
-  return a.mask && !a.z && !a.dzscale && !a.dyhat && a.C % 8 == 0 && a.lddz % 8 == 0 &&
-         a.ldy % 8 == 0 && a.ldy2 % 8 == 0 && a.lddy % 8 == 0 && a.lddy2 % 8 == 0 &&
-         (uintptr_t)a.dz % 16 == 0;
+  const BnBwdPlan p = bn_bwd_apply_plan(a);
+  if (p.refusal) return hipErrorInvalidValue;
+  bool row = true;
+  const hipError_t e = dispatch_dtype2(dtype, dz_f32, [&](auto t, auto tz) {
+    using T = TAG_T(t);
+    using TZ = TAG_T(tz);
+    if (!p.wide) {   // z, dzscale and dyhat by their pointers
+      hipLaunchKernelGGL((bn_bwd_apply_kernel<T, TZ>), dim3(grid_for(a.M * a.C)), dim3(256), 0, s, a);
+      return;
+    }
+    const dim3 g = grid8(a.M, a.C);
+    switch (bwd_key(p.gate, p.term, p.dyhat, 0)) {
+#define BN_CASE(HZ, HS, HD) \
+  case bwd_key(HZ, HS, HD, 0): hipLaunchKernelGGL((bn_bwd_apply8_kernel<T, TZ, HZ, HS, HD>), g, dim3(256), 0, s, a); break;
+      BN_CASE(2, 2, 0) BN_CASE(2, 1, 1) BN_CASE(2, 1, 0) BN_CASE(2, 0, 1) BN_CASE(2, 0, 0)
+      BN_CASE(1, 1, 1) BN_CASE(1, 1, 0) BN_CASE(1, 0, 1) BN_CASE(1, 0, 0)
+      BN_CASE(0, 1, 1) BN_CASE(0, 1, 0) BN_CASE(0, 0, 1) BN_CASE(0, 0, 0)
+#undef BN_CASE
+      default: row = false;
+    }
+  });
+  return row ? e : hipErrorInvalidValue;
 }
 
 hipError_t launch_bn_bwd_reduce_dual(int dtype, const BnBwdArgs& a, hipStream_t s) {
-  const int cg_n = a.C / 8;
-  const dim3 g(a.rb, cg_n > 256 ? ceil_div(cg_n, 256) : 1);
-  if (dtype == SEG_BF16) {
-    if (!dual_ok<bf16_t>(a)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(bn_bwd_reduce8_dual_kernel<bf16_t>, g, dim3(256), 0, s, a);
-  } else if (dtype == SEG_F16) {
-    if (!dual_ok<f16_t>(a)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(bn_bwd_reduce8_dual_kernel<f16_t>, g, dim3(256), 0, s, a);
-  } else {
-    if (!dual_ok<float>(a)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(bn_bwd_reduce8_dual_kernel<float>, g, dim3(256), 0, s, a);
-  }
-  return hipGetLastError();
+  if (bn_bwd_dual_plan(a).refusal) return hipErrorInvalidValue;
+  return dispatch_dtype(dtype, [&](auto t) {
+    hipLaunchKernelGGL(bn_bwd_reduce8_dual_kernel<TAG_T(t)>, dim3(a.rb, blocks_y(a.C)), dim3(256), 0, s, a);
+  });
 }
 
 hipError_t launch_bn_bwd_apply_dual(int dtype, const BnBwdArgs& a, hipStream_t s) {
-  const dim3 g = grid8(a.M, a.C);
-  if (dtype == SEG_BF16) {
-    if (!dual_ok<bf16_t>(a)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(bn_bwd_apply8_dual_kernel<bf16_t>, g, dim3(256), 0, s, a);
-  } else if (dtype == SEG_F16) {
-    if (!dual_ok<f16_t>(a)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(bn_bwd_apply8_dual_kernel<f16_t>, g, dim3(256), 0, s, a);
-  } else {
-    if (!dual_ok<float>(a)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(bn_bwd_apply8_dual_kernel<float>, g, dim3(256), 0, s, a);
-  }
-  return hipGetLastError();
+  if (bn_bwd_dual_plan(a).refusal) return hipErrorInvalidValue;
+  return dispatch_dtype(dtype, [&](auto t) {
+    hipLaunchKernelGGL(bn_bwd_apply8_dual_kernel<TAG_T(t)>, grid8(a.M, a.C), dim3(256), 0, s, a);
+  });
 }
 
 hipError_t launch_moving_update(float* mov_mean, float* mov_var, const float* bmean,

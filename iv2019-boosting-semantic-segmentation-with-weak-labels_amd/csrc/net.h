@@ -223,8 +223,6 @@ struct seg_ctx {
   // workspace
   float* slab = nullptr;
   size_t slab_floats = 0;
-  float* stat_scratch = nullptr;
-  size_t stat_scratch_floats = 0;
   // linear BN-backward fold (lbf.h), on unless seg_set_lbf(ctx, 0): 16-bit bottleneck units
   // whose conv3 expands (co >= 2 ci, ci % 64 == 0: every unit of R50). Compute-stream scratch (used in
   // order by one layer at a time): the scaled data-gradient weights, the D-scaled weights, H

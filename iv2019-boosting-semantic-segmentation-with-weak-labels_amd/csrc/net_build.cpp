@@ -134,7 +134,7 @@ int alloc_conv(seg_ctx* c, ConvL& L, int N, int H, int W, int ldy = 0) {
   if (int r = dalloc(c, &L.stats_part, (size_t)conv_nt_mtiles(M) * L.co * 2)) return r;
   if (c->gn) {
     const long hw = (long)L.Ho * L.Wo;
-    L.rb = bn_bwd_rowblocks(hw, L.co);
+    L.rb = bn_bwd_rowblocks(hw);
     if (int r = dalloc(c, &L.bwd_part, (size_t)N * L.rb * L.co * 2)) return r;
     if (int r = dalloc(c, &L.gn_part, (size_t)N * gn_chunks(hw) * L.co * 2)) return r;
     float* sv;
@@ -147,11 +147,9 @@ int alloc_conv(seg_ctx* c, ConvL& L, int N, int H, int W, int ldy = 0) {
     if (int r = dalloc(c, &L.st_dev, (size_t)N)) return r;
     HIPCALL(c, hipMemcpy(L.st_dev, L.st_img.data(), N * sizeof(BnState), hipMemcpyHostToDevice));
   } else {
-    L.rb = bn_bwd_rowblocks(M, L.co);
+    L.rb = bn_bwd_rowblocks(M);
     if (int r = dalloc(c, &L.bwd_part, (size_t)L.rb * L.co * 2)) return r;
   }
-  size_t need = (size_t)((conv_nt_mtiles(M) + 63) / 64) * L.co * 3;
-  c->stat_scratch_floats = std::max(c->stat_scratch_floats, need);
   return 0;
 }
 
@@ -528,8 +526,7 @@ int build_workspace(seg_ctx* c) {
     if (int r = dalloc(c, &c->stem_wpad, (size_t)st.co * 256)) return r;
   }
   c->slab_floats = slab;
-  if (int r = dalloc(c, &c->slab, slab)) return r;
-  return dalloc(c, &c->stat_scratch, std::max<size_t>(c->stat_scratch_floats, 16));
+  return dalloc(c, &c->slab, slab);
 }
 
 // linear BN-backward fold: per-layer coefficients and the shared scratch (lbf.h)

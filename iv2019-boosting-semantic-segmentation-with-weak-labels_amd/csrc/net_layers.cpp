@@ -229,7 +229,7 @@ int conv_forward(Step& S, int li, const Act& x) {
   if (c->bn_infer) return 0;   // is_training=False: the statistics were set for every layer
                                // by one launch at the start of the forward
   const bool sync = c->sync_fn != nullptr;
-  HIPCALL(c, launch_bn_stats_finalize(L.stats_part, M, L.co, conv_nt_plan(S.dt, 0, a).stat_rows, c->stat_scratch,
+  HIPCALL(c, launch_bn_stats_finalize(L.stats_part, M, L.co, conv_nt_plan(S.dt, 0, a).stat_rows,
                                       c->params + L.g_off, L.st, S.s, sync ? c->sync_pack : nullptr));
   if (sync) {
     if (int r = sync_exchange(c, c->sync_pack, 2L * L.co, S.s)) return r;
@@ -344,7 +344,7 @@ int bn_backward(Step& S, int li, const Act& dz, int dz_f32, const Act* z, const 
   a.dshift = dshift;
   a.reduce_dyhat = reduce_only && dyhat_out ? 1 : 0;
   if (cs_out) { a.cs_part = cs_out; a.beta = c->params + L.b_off; }
-  if ((dshift || a.reduce_dyhat || cs_out) && !a.mask)
+  if (bn_bwd_reduce_plan(S.dt, a).refusal)
     return set_err(&c->err, -EINVAL, "bn_backward %s: shift / reduce-side dyhat need the ReLU bits", L.name.c_str());
   const double esz = seg_half(S.dt) ? 2.0 : 4.0, zsz = dz_f32 ? 4.0 : esz;
   const double me = a.M * (double)a.C * 1e-9;

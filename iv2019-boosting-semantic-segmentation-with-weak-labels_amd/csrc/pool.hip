@@ -555,16 +555,11 @@ hipError_t launch_maxpool_fwd(int dtype, const void* x, int N, int H, int W, int
   if (C % 8 || ldx % 8 || ldy % 8) return hipErrorInvalidValue;
   if ((long)N * Ho * Wo * C / 8 >= (1L << 31)) return hipErrorInvalidValue;   // 32-bit decode
   dim3 g(grid_for((long)N * Ho * Wo * C / 8));
-  if (dtype == SEG_BF16)
-    hipLaunchKernelGGL(maxpool_fwd_kernel<bf16_t>, g, dim3(256), 0, s, (const bf16_t*)x, N, H, W, C,
-                       ldx, (bf16_t*)y, Ho, Wo, ldy, pad_h, pad_w, (uint8_t*)arg);
-  else if (dtype == SEG_F16)
-    hipLaunchKernelGGL(maxpool_fwd_kernel<f16_t>, g, dim3(256), 0, s, (const f16_t*)x, N, H, W, C,
-                       ldx, (f16_t*)y, Ho, Wo, ldy, pad_h, pad_w, (uint8_t*)arg);
-  else
-    hipLaunchKernelGGL(maxpool_fwd_kernel<float>, g, dim3(256), 0, s, (const float*)x, N, H, W, C,
-                       ldx, (float*)y, Ho, Wo, ldy, pad_h, pad_w, (uint8_t*)arg);
-  return hipGetLastError();
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = TAG_T(t);
+    hipLaunchKernelGGL(maxpool_fwd_kernel<T>, g, dim3(256), 0, s, (const T*)x, N, H, W, C, ldx,
+                       (T*)y, Ho, Wo, ldy, pad_h, pad_w, (uint8_t*)arg);
+  });
 }
 
 hipError_t launch_bn_relu_maxpool_fwd(int dtype, const void* y, int N, int H, int W, int ldy,
@@ -575,16 +570,11 @@ hipError_t launch_bn_relu_maxpool_fwd(int dtype, const void* y, int N, int H, in
     return hipErrorInvalidValue;
   if ((long)N * Ho * Wo * 8 >= (1L << 31)) return hipErrorInvalidValue;   // 32-bit decode
   const dim3 g((unsigned)ceil_div((long)N * Ho * Wo * 8, 256));
-  if (dtype == SEG_BF16)
-    hipLaunchKernelGGL(bn_relu_maxpool_kernel<bf16_t>, g, dim3(256), 0, s, (const bf16_t*)y, N, H, W,
-                       ldy, mean, scale, beta, mask, (bf16_t*)p, Ho, Wo, ldp, arg);
-  else if (dtype == SEG_F16)
-    hipLaunchKernelGGL(bn_relu_maxpool_kernel<f16_t>, g, dim3(256), 0, s, (const f16_t*)y, N, H, W,
-                       ldy, mean, scale, beta, mask, (f16_t*)p, Ho, Wo, ldp, arg);
-  else
-    hipLaunchKernelGGL(bn_relu_maxpool_kernel<float>, g, dim3(256), 0, s, (const float*)y, N, H, W,
-                       ldy, mean, scale, beta, mask, (float*)p, Ho, Wo, ldp, arg);
-  return hipGetLastError();
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = TAG_T(t);
+    hipLaunchKernelGGL(bn_relu_maxpool_kernel<T>, g, dim3(256), 0, s, (const T*)y, N, H, W, ldy,
+                       mean, scale, beta, mask, (T*)p, Ho, Wo, ldp, arg);
+  });
 }
 
 hipError_t launch_maxpool_bwd(int dtype, const void* arg, int N, int H, int W, int C,
@@ -592,41 +582,25 @@ hipError_t launch_maxpool_bwd(int dtype, const void* arg, int N, int H, int W, i
                               int pad_h, int pad_w, hipStream_t s) {
   if (C % 8 || lddy % 8 || lddx % 8) return hipErrorInvalidValue;
   if ((long)N * H * W * C / 8 >= (1L << 31)) return hipErrorInvalidValue;   // 32-bit decode
-  if (C == 64 && pad_h == 0 && pad_w == 0 && H == 2 * Ho && W == 2 * Wo && (dtype == SEG_BF16 || dtype == SEG_F16) &&
-      (long)N * Ho < 65536) {   // the stem pool (16-bit): LDS-staged pooled tiles
-    dim3 g((unsigned)ceil_div(W, 64), (unsigned)(N * Ho));
-    if (dtype == SEG_BF16)
-      hipLaunchKernelGGL(maxpool_bwd_tile_kernel<bf16_t>, g, dim3(256), 0, s, (const uint8_t*)arg, H, W,
-                         (const bf16_t*)dy, Ho, Wo, lddy, (bf16_t*)dx, lddx);
-    else
-      hipLaunchKernelGGL(maxpool_bwd_tile_kernel<f16_t>, g, dim3(256), 0, s, (const uint8_t*)arg, H, W,
-                         (const f16_t*)dy, Ho, Wo, lddy, (f16_t*)dx, lddx);
-    return hipGetLastError();
-  }
-  if (C == 64 && (long)N * H < 65536) {   // the stem pool: one row of the input per grid row
-    dim3 g((unsigned)ceil_div((long)W * 8, 256), (unsigned)(N * H));
-    if (dtype == SEG_BF16)
-      hipLaunchKernelGGL(maxpool_bwd_row_kernel<bf16_t>, g, dim3(256), 0, s, (const uint8_t*)arg, H, W,
-                         (const bf16_t*)dy, Ho, Wo, lddy, (bf16_t*)dx, lddx, pad_h, pad_w);
-    else if (dtype == SEG_F16)
-      hipLaunchKernelGGL(maxpool_bwd_row_kernel<f16_t>, g, dim3(256), 0, s, (const uint8_t*)arg, H, W,
-                         (const f16_t*)dy, Ho, Wo, lddy, (f16_t*)dx, lddx, pad_h, pad_w);
-    else
-      hipLaunchKernelGGL(maxpool_bwd_row_kernel<float>, g, dim3(256), 0, s, (const uint8_t*)arg, H, W,
-                         (const float*)dy, Ho, Wo, lddy, (float*)dx, lddx, pad_h, pad_w);
-    return hipGetLastError();
-  }
-  dim3 g(grid_for((long)N * H * W * C / 8));
-  if (dtype == SEG_BF16)
-    hipLaunchKernelGGL(maxpool_bwd_kernel<bf16_t>, g, dim3(256), 0, s, (const uint8_t*)arg, N, H, W,
-                       C, (const bf16_t*)dy, Ho, Wo, lddy, (bf16_t*)dx, lddx, pad_h, pad_w);
-  else if (dtype == SEG_F16)
-    hipLaunchKernelGGL(maxpool_bwd_kernel<f16_t>, g, dim3(256), 0, s, (const uint8_t*)arg, N, H, W,
-                       C, (const f16_t*)dy, Ho, Wo, lddy, (f16_t*)dx, lddx, pad_h, pad_w);
-  else
-    hipLaunchKernelGGL(maxpool_bwd_kernel<float>, g, dim3(256), 0, s, (const uint8_t*)arg, N, H, W,
-                       C, (const float*)dy, Ho, Wo, lddy, (float*)dx, lddx, pad_h, pad_w);
-  return hipGetLastError();
+  const bool stem = C == 64;   // the stem pool: kernels of their own
+  const bool tile = stem && pad_h == 0 && pad_w == 0 && H == 2 * Ho && W == 2 * Wo && seg_half(dtype) &&
+                    (long)N * Ho < 65536;   // 16-bit: LDS-staged pooled tiles
+  const bool row = stem && (long)N * H < 65536;   // one row of the input per grid row
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = TAG_T(t);
+    const uint8_t* am = (const uint8_t*)arg;
+    if (tile) {
+      if constexpr (sizeof(T) == 2)   // (no fp32 instantiation)
+        hipLaunchKernelGGL(maxpool_bwd_tile_kernel<T>, dim3((unsigned)ceil_div(W, 64), (unsigned)(N * Ho)),
+                           dim3(256), 0, s, am, H, W, (const T*)dy, Ho, Wo, lddy, (T*)dx, lddx);
+    } else if (row) {
+      hipLaunchKernelGGL(maxpool_bwd_row_kernel<T>, dim3((unsigned)ceil_div((long)W * 8, 256), (unsigned)(N * H)),
+                         dim3(256), 0, s, am, H, W, (const T*)dy, Ho, Wo, lddy, (T*)dx, lddx, pad_h, pad_w);
+    } else {
+      hipLaunchKernelGGL(maxpool_bwd_kernel<T>, dim3(grid_for((long)N * H * W * C / 8)), dim3(256), 0, s,
+                         am, N, H, W, C, (const T*)dy, Ho, Wo, lddy, (T*)dx, lddx, pad_h, pad_w);
+    }
+  });
 }
 
 hipError_t launch_add_strided(int dtype, void* dx, int H, int W, int lddx, const void* g, int N,
@@ -634,16 +608,11 @@ hipError_t launch_add_strided(int dtype, void* dx, int H, int W, int lddx, const
   if (C % 8 || lddx % 8 || ldg % 8) return hipErrorInvalidValue;
   if ((long)N * Ho * Wo * C / 8 >= (1L << 31)) return hipErrorInvalidValue;   // 32-bit decode
   dim3 gr(grid_for((long)N * Ho * Wo * C / 8));
-  if (dtype == SEG_BF16)
-    hipLaunchKernelGGL(add_strided_kernel<bf16_t>, gr, dim3(256), 0, s, (bf16_t*)dx, H, W, lddx,
-                       (const bf16_t*)g, N, Ho, Wo, C, ldg, stride);
-  else if (dtype == SEG_F16)
-    hipLaunchKernelGGL(add_strided_kernel<f16_t>, gr, dim3(256), 0, s, (f16_t*)dx, H, W, lddx,
-                       (const f16_t*)g, N, Ho, Wo, C, ldg, stride);
-  else
-    hipLaunchKernelGGL(add_strided_kernel<float>, gr, dim3(256), 0, s, (float*)dx, H, W, lddx,
-                       (const float*)g, N, Ho, Wo, C, ldg, stride);
-  return hipGetLastError();
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = TAG_T(t);
+    hipLaunchKernelGGL(add_strided_kernel<T>, gr, dim3(256), 0, s, (T*)dx, H, W, lddx, (const T*)g,
+                       N, Ho, Wo, C, ldg, stride);
+  });
 }
 
 hipError_t launch_grid_rowreduce(int dtype, const void* x, int N, int H, int W, int C, int ldx,
@@ -651,25 +620,11 @@ hipError_t launch_grid_rowreduce(int dtype, const void* x, int N, int H, int W, 
   if (g.total_ccells > SEG_MAX_CELLS) return hipErrorInvalidValue;
   dim3 gr(N * H);
   const bool v8 = C % 8 == 0 && ldx % 8 == 0 && C / 8 <= 256 && 256 % (C / 8) == 0 && g.total_ccells <= 12;
-  if (v8) {
-    if (dtype == SEG_BF16)
-      hipLaunchKernelGGL((grid_rowreduce8_kernel<bf16_t>), gr, dim3(256), 0, s, (const bf16_t*)x, N, H, W, C, ldx, g, part);
-    else if (dtype == SEG_F16)
-      hipLaunchKernelGGL((grid_rowreduce8_kernel<f16_t>), gr, dim3(256), 0, s, (const f16_t*)x, N, H, W, C, ldx, g, part);
-    else
-      hipLaunchKernelGGL((grid_rowreduce8_kernel<float>), gr, dim3(256), 0, s, (const float*)x, N, H, W, C, ldx, g, part);
-    return hipGetLastError();
-  }
-  if (dtype == SEG_BF16)
-    hipLaunchKernelGGL(grid_rowreduce_kernel<bf16_t>, gr, dim3(256), 0, s, (const bf16_t*)x, N, H,
-                       W, C, ldx, g, part);
-  else if (dtype == SEG_F16)
-    hipLaunchKernelGGL(grid_rowreduce_kernel<f16_t>, gr, dim3(256), 0, s, (const f16_t*)x, N, H,
-                       W, C, ldx, g, part);
-  else
-    hipLaunchKernelGGL(grid_rowreduce_kernel<float>, gr, dim3(256), 0, s, (const float*)x, N, H, W,
-                       C, ldx, g, part);
-  return hipGetLastError();
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = TAG_T(t);
+    if (v8) hipLaunchKernelGGL(grid_rowreduce8_kernel<T>, gr, dim3(256), 0, s, (const T*)x, N, H, W, C, ldx, g, part);
+    else hipLaunchKernelGGL(grid_rowreduce_kernel<T>, gr, dim3(256), 0, s, (const T*)x, N, H, W, C, ldx, g, part);
+  });
 }
 
 hipError_t launch_grid_colreduce(int dtype, const float* part, int N, int H, int W, int C,
@@ -680,13 +635,9 @@ hipError_t launch_grid_colreduce(int dtype, const float* part, int N, int H, int
   for (int i = 0; i < SEG_MAX_GRIDS; ++i) o.p[i] = i < g.n ? outs[i] : nullptr;
   for (int i = 0; i < g.n; ++i) total += (long)N * g.kr[i] * g.kc[i] * C;
   dim3 gr(ceil_div(total, 256));
-  if (dtype == SEG_BF16)
-    hipLaunchKernelGGL(grid_colreduce_kernel<bf16_t>, gr, dim3(256), 0, s, part, N, H, C, g, o);
-  else if (dtype == SEG_F16)
-    hipLaunchKernelGGL(grid_colreduce_kernel<f16_t>, gr, dim3(256), 0, s, part, N, H, C, g, o);
-  else
-    hipLaunchKernelGGL(grid_colreduce_kernel<float>, gr, dim3(256), 0, s, part, N, H, C, g, o);
-  return hipGetLastError();
+  return dispatch_dtype(dtype, [&](auto t) {
+    hipLaunchKernelGGL(grid_colreduce_kernel<TAG_T(t)>, gr, dim3(256), 0, s, part, N, H, C, g, o);
+  });
 }
 
 hipError_t launch_resize_fwd(int dtype, const void* x, int N, int hi, int wi, int C, int ldx,
@@ -694,16 +645,11 @@ hipError_t launch_resize_fwd(int dtype, const void* x, int N, int hi, int wi, in
   if (C % 8 || ldx % 8 || ldy % 8) return hipErrorInvalidValue;
   if ((long)N * Ho * Wo * C / 8 >= (1L << 31)) return hipErrorInvalidValue;   // 32-bit decode
   dim3 gr(grid_for((long)N * Ho * Wo * C / 8));
-  if (dtype == SEG_BF16)
-    hipLaunchKernelGGL(resize_fwd_kernel<bf16_t>, gr, dim3(256), 0, s, (const bf16_t*)x, N, hi, wi,
-                       C, ldx, (bf16_t*)y, Ho, Wo, ldy);
-  else if (dtype == SEG_F16)
-    hipLaunchKernelGGL(resize_fwd_kernel<f16_t>, gr, dim3(256), 0, s, (const f16_t*)x, N, hi, wi,
-                       C, ldx, (f16_t*)y, Ho, Wo, ldy);
-  else
-    hipLaunchKernelGGL(resize_fwd_kernel<float>, gr, dim3(256), 0, s, (const float*)x, N, hi, wi, C,
-                       ldx, (float*)y, Ho, Wo, ldy);
-  return hipGetLastError();
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = TAG_T(t);
+    hipLaunchKernelGGL(resize_fwd_kernel<T>, gr, dim3(256), 0, s, (const T*)x, N, hi, wi, C, ldx,
+                       (T*)y, Ho, Wo, ldy);
+  });
 }
 
 hipError_t launch_psp_input_bwd(int dtype, const void* dcat, int ldcat, const GridSpec& g,
@@ -714,14 +660,9 @@ hipError_t launch_psp_input_bwd(int dtype, const void* dcat, int ldcat, const Gr
   for (int i = 0; i < SEG_MAX_GRIDS; ++i) ip.p[i] = i < g.n ? dpooled[i] : nullptr;
   if ((long)N * H * W * C / 8 >= (1L << 31)) return hipErrorInvalidValue;   // 32-bit decode
   dim3 gr(grid_for((long)N * H * W * C / 8));
-  if (dtype == SEG_BF16)
-    hipLaunchKernelGGL(psp_input_bwd_kernel<bf16_t>, gr, dim3(256), 0, s, (const bf16_t*)dcat, ldcat,
-                       g, ip, N, H, W, C, (bf16_t*)dx, lddx);
-  else if (dtype == SEG_F16)
-    hipLaunchKernelGGL(psp_input_bwd_kernel<f16_t>, gr, dim3(256), 0, s, (const f16_t*)dcat, ldcat,
-                       g, ip, N, H, W, C, (f16_t*)dx, lddx);
-  else
-    hipLaunchKernelGGL(psp_input_bwd_kernel<float>, gr, dim3(256), 0, s, (const float*)dcat, ldcat, g,
-                       ip, N, H, W, C, (float*)dx, lddx);
-  return hipGetLastError();
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = TAG_T(t);
+    hipLaunchKernelGGL(psp_input_bwd_kernel<T>, gr, dim3(256), 0, s, (const T*)dcat, ldcat, g, ip,
+                       N, H, W, C, (T*)dx, lddx);
+  });
 }

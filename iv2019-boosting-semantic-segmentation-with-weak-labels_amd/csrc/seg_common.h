@@ -171,3 +171,33 @@ __device__ __forceinline__ float wave_sum(float v) {
   } while (0)
 
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
+
+// ---- element-type dispatch of the launchers ------------------------------------------
+// f(tag) launches for the element type tag names (TAG_T(tag)); bf16, fp16, else fp32. Returns
+// hipGetLastError(), like decision_head::dispatch_heads.
+template <typename T> struct TypeTag { typedef T type; };
+#define TAG_T(tag) typename decltype(tag)::type
+
+template <typename F>
+inline hipError_t dispatch_dtype(int dtype, F f) {
+  if (dtype == SEG_BF16) f(TypeTag<bf16_t>{});
+  else if (dtype == SEG_F16) f(TypeTag<f16_t>{});
+  else f(TypeTag<float>{});
+  return hipGetLastError();
+}
+
+// f(tag, tag2) for launches of two types: the storage type T and a second tensor that is T or,
+// with second_f32, fp32 (fp32 storage: always fp32)
+template <typename F>
+inline hipError_t dispatch_dtype2(int dtype, int second_f32, F f) {
+  if (dtype == SEG_BF16) {
+    if (second_f32) f(TypeTag<bf16_t>{}, TypeTag<float>{});
+    else f(TypeTag<bf16_t>{}, TypeTag<bf16_t>{});
+  } else if (dtype == SEG_F16) {
+    if (second_f32) f(TypeTag<f16_t>{}, TypeTag<float>{});
+    else f(TypeTag<f16_t>{}, TypeTag<f16_t>{});
+  } else {
+    f(TypeTag<float>{}, TypeTag<float>{});
+  }
+  return hipGetLastError();
+}

@@ -330,7 +330,8 @@ def _variant_kw(cuda, dtype, a, M, C, variant):
     return kw
 
 
-# one case per branch of bwd_reduce_t / bwd_apply_t: (id, variant, dyhat, reduce_only, frozen)
+# one case per row of the plan table (batch norm; bits + dzscale, with and without
+# dyhat: test_group_norm_apply_gate): (id, variant, dyhat, reduce_only, frozen)
 BRANCHES = [
     ("ungated", (), False, False, False),
     ("z", ("z",), False, False, False),
@@ -345,6 +346,7 @@ BRANCHES = [
     ("z+dyhat", ("z",), True, False, False),
     ("bits+dyhat", ("bits",), True, False, False),
     ("z+dzscale+dyhat", ("z", "dzscale"), True, False, False),
+    ("dzscale+dyhat", ("dzscale",), True, False, False),
     ("frozen", ("bits",), False, False, True),
 ]
 
@@ -379,22 +381,23 @@ def test_backward_branches(cuda, dtype, branch):
 
 
 def test_group_norm_apply_gate(cuda):
-    """bits + dzscale + dyhat, the group-norm apply: with the bits the reduce has no dzscale
-    instantiation (group norm passes gamma to the apply alone), so the sums are those of the gated
-    dz and the apply's dy carries dzscale; dyhat is stored before it"""
-    for dtype in ("bf16", "fp16", "fp32"):
+    """bits + dzscale with and without dyhat, the group-norm apply: with the bits the reduce drops
+    dzscale (group norm passes gamma to the apply alone), so the sums are those of the gated dz
+    and the apply's dy carries dzscale; dyhat is stored before it"""
+    for dtype, dyhat in [(t, h) for t in ("bf16", "fp16", "fp32") for h in (True, False)]:
         M, C = 391, 128
         a = R.layer_inputs(M, C, dtype, seed=43)
         kw = _variant_kw(cuda, dtype, a, M, C, ("bits", "dzscale"))
-        b = Bwd(cuda, dtype, a, M, C, kw, want_dyhat=True)
+        b = Bwd(cuda, dtype, a, M, C, kw, want_dyhat=dyhat)
         assert _run_bwd(b) == 0
         ref_sums = R.bwd_ref(a["dz"], a["y"], a["mean"], a["invstd"], dtype, mask=kw["mask"])
         ref = R.bwd_ref(a["dz"], a["y"], a["mean"], a["invstd"], dtype, **kw)
         got = b.sums()
         res = R.bwd_sums_check(got, ref_sums)
-        res.update(R.dyhat_check(_host(b.dyhat), ref))
+        if dyhat:
+            res.update(R.dyhat_check(_host(b.dyhat), ref))
         res.update(R.dy_check(_host(b.dy), ref, a["scale"], got["sdy"], got["sdyx"], dtype)[0])
-        _record("bwd_bits+dzscale+dyhat", dtype, res)
+        _record("bwd_bits+dzscale" + ("+dyhat" if dyhat else ""), dtype, res)
 
 
 @pytest.mark.parametrize("dtype,M,C", BWD_CASES)

@@ -1,8 +1,9 @@
 """One training step's gradients, losses and low-res logits from the working-tree library and
 from an A/B build (SEG_HIP_LIB), each in its own child process: max difference per tensor class
 (conv weights, BN gammas / betas by parameter kind; losses; logits).
-    python tools/ab_grads.py ab/<variant>/libseg_hip.so [dtype pyramid height width nb_pp,nb_pb,nb_pi]
-Default: the C2 step (bf16 aspp 1024 2048 4,0,0)."""
+    python tools/ab_grads.py ab/<variant>/libseg_hip.so [dtype pyramid height width nb_pp,nb_pb,nb_pi] [--self]
+Default: the C2 step (bf16 aspp 1024 2048 4,0,0). --self runs the A/B build against itself: which
+tensor classes repeat from run to run at all."""
 import os
 import subprocess
 import sys
@@ -50,8 +51,12 @@ def run(lib, out, cfg):
     return np.load(out)
 
 
+own = "--self" in sys.argv
+if own:
+    sys.argv.remove("--self")
 cfg = sys.argv[2:7] if len(sys.argv) >= 7 else ["bf16", "aspp", "1024", "2048", "4,0,0"]
-a = run(None, "/tmp/ab_grads_a.npz", cfg)
+a = run(os.path.abspath(sys.argv[1]) if own else None, "/tmp/ab_grads_a.npz", cfg)
+print("A/B build against itself" if own else "working tree against the A/B build")
 b = run(os.path.abspath(sys.argv[1]), "/tmp/ab_grads_b.npz", cfg)
 worst = 0.0
 for name in ("losses", "logits"):

@@ -2,9 +2,11 @@
 to gfx950 assembly (device side only) and compares, per kernel, the descriptor values
 (next_free_vgpr, accum_offset, next_free_sgpr, private_segment_fixed_size, static LDS), the
 instruction count and the instruction text.
-    python tools/kernel_static_ab.py <parent tree> [<this tree>] [--identical REGEX] [--keep DIR]
-Kernel names are demangled and conv_nt_v2_kernel's former MFMA-shape argument (always 16) is
-dropped, so the two trees' instantiations pair up. Prints one row per kernel whose text differs
+    python tools/kernel_static_ab.py <parent tree> [<this tree>] [--identical REGEX] [--gone REGEX]... [--keep DIR]
+Kernel names are demangled and conv_nt_v2_kernel's former MFMA-shape argument (always 16) and the
+scalar BN kernels' former vector width (always 1) are dropped, so the two trees' instantiations
+pair up. --gone names parent kernels that must have no counterpart here; any other unpaired
+kernel fails. Prints one row per kernel whose text differs
 and a summary per file; exits 1 if a kernel matching --identical differs, if any differing kernel
 has scratch, or a different accum_offset or allocated VGPR count (next_free_vgpr rounded up to the
 allocation granule of 8)."""
@@ -50,6 +52,9 @@ def normal_name(d):
         args = re.findall(r"Li\d+E", m.group(2))
         del args[6]
         return m.group(1) + "".join(args) + m.group(3)
+    # the scalar BN kernels' former vector width (always 1), demangled or, for fp16, mangled
+    if re.search(r"bn_(apply|bwd_reduce|bwd_apply)_kernel", d):
+        return re.sub(r"Li1E(?=EEv\d+Bn\w+Args$)", "", re.sub(r", 1(?=>\(Bn\w+Args\)$)", "", d))
     return d
 
 
@@ -81,6 +86,11 @@ def main():
         i = args.index("--identical")
         ident = re.compile(args[i + 1])
         del args[i:i + 2]
+    gone = []
+    while "--gone" in args:   # a parent kernel expected to have no counterpart here (repeatable)
+        i = args.index("--gone")
+        gone.append(re.compile(args[i + 1]))
+        del args[i:i + 2]
     tmp = None
     if "--keep" in args:   # keep (and reuse) the assembly files in DIR
         i = args.index("--keep")
@@ -99,6 +109,10 @@ def main():
     print("file kernel | vgpr accum_offset sgpr scratch static_lds instructions: parent -> this tree")
     for f in files:
         ka, kb = kernels(asm[("a", f)]), kernels(asm[("b", f)])
+        for k in [k for k in ka if any(g.search(k) for g in gone)]:
+            print(f"{f} {k}: " + ("expected to be gone, still here" if k in kb else "gone, as expected"))
+            bad += k in kb
+            del ka[k]
         if set(ka) != set(kb):
             print(f"{f}: kernel sets differ: {sorted(set(ka) ^ set(kb))}")
             bad += 1
