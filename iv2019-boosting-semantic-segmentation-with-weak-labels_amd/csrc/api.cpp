@@ -175,43 +175,56 @@ int seg_set_bn_inference(seg_ctx* c, int on) {
   return 0;
 }
 
-// utils._replacevoids on the caller's cid map: -1 -> max + 1; anything below -1 is refused.
-// who prefixes the message ("who: ") where the entry names itself in its errors.
-static int normalise_cid_map(seg_ctx* c, const char* who, const int32_t* cid_map, int n_map,
-                             int* map) {
+// "who: " in front of the messages of the entries that name themselves in their errors
+static std::string prefix(const char* who) { return who ? std::string(who) + ": " : std::string(); }
+
+static int check_aligned16(seg_ctx* c, const char* who, const void* p, const char* name) {
+  if (reinterpret_cast<uintptr_t>(p) & 15)
+    return set_err(&c->err, -EINVAL, "%s%s must be 16-byte aligned", prefix(who).c_str(), name);
+  return 0;
+}
+
+// What the four decision entries (seg_predict, seg_tta_decisions, seg_window_decisions,
+// seg_crf_decisions) ask of the two pointers, replace_voids, the cid map and the output size.
+// max_rv: the highest replace_voids mode of the entry (2 for seg_predict, else 1); kind: what its
+// probabilities are ("averaged", "refined") in the refusal of mode 2. Writes the map of
+// utils._replacevoids (-1 -> max + 1; anything below -1 is refused) to map.
+static int check_decision_args(seg_ctx* c, const char* who, int max_rv, const char* kind,
+                               int replace_voids, const int32_t* cid_map, int n_map, int out_h,
+                               int out_w, const int32_t* decisions_out, int* map) {
+  const std::string pre = prefix(who);
+  std::string* err = &c->err;
+  if (!cid_map) return set_err(err, -EINVAL, "%snull cid_map", pre.c_str());
+  if (!decisions_out) return set_err(err, -EINVAL, "%snull decisions_out", pre.c_str());
+  if (replace_voids == 2 && max_rv < 2)
+    return set_err(err, -EINVAL, "%sreplace_voids = 2 (the PREDICT order on resized "
+                   "probabilities) is not defined for %s probabilities; use 1", pre.c_str(), kind);
+  if (replace_voids < 0 || replace_voids > max_rv)
+    return set_err(err, -EINVAL, "%sreplace_voids = %d (%s)", pre.c_str(), replace_voids,
+                   max_rv == 2 ? "0, 1 or 2" : "0 or 1");
+  if (n_map != c->tables.n_pp)
+    return set_err(err, -EINVAL, "%scid_map has %d entries, the model has %d training classes",
+                   pre.c_str(), n_map, c->tables.n_pp);
+  if (out_h < 1 || out_w < 1)
+    return set_err(err, -EINVAL, "%sbad output size out_h x out_w = %dx%d", pre.c_str(), out_h, out_w);
   int mx = -1;
   for (int i = 0; i < n_map; ++i) mx = std::max(mx, (int)cid_map[i]);
   for (int i = 0; i < n_map; ++i) {
     if (cid_map[i] < -1)
-      return set_err(&c->err, -EINVAL, "%s%scid_map[%d] = %d", who ? who : "", who ? ": " : "", i,
-                     cid_map[i]);
+      return set_err(err, -EINVAL, "%scid_map[%d] = %d", pre.c_str(), i, cid_map[i]);
     map[i] = cid_map[i] == -1 ? mx + 1 : cid_map[i];
   }
   return 0;
 }
 
-// What the multi-entry heads (seg_tta_decisions, seg_window_decisions) ask of replace_voids, the
-// cid map's length, the output size and mean_probs_out, which needs the output to have the size
-// probabilities are averaged at: avg_h x avg_w, "the <avg_name> size" in the message.
-static int check_averaged_head(seg_ctx* c, const char* who, int replace_voids, int n_map, int out_h,
-                               int out_w, const float* mean_probs_out, const char* avg_name,
-                               int avg_h, int avg_w) {
-  if (replace_voids == 2)
-    return set_err(&c->err, -EINVAL, "%s: replace_voids = 2 (the PREDICT order on resized "
-                   "probabilities) is not defined for averaged probabilities; use 1", who);
-  if (replace_voids < 0 || replace_voids > 1)
-    return set_err(&c->err, -EINVAL, "%s: replace_voids = %d (0 or 1)", who, replace_voids);
-  if (n_map != c->tables.n_pp)
-    return set_err(&c->err, -EINVAL, "%s: cid map has %d entries, the model has %d training classes",
-                   who, n_map, c->tables.n_pp);
-  if (out_h < 1 || out_w < 1)
-    return set_err(&c->err, -EINVAL, "%s: bad output size %dx%d", who, out_h, out_w);
-  if (mean_probs_out && (reinterpret_cast<uintptr_t>(mean_probs_out) & 15))
-    return set_err(&c->err, -EINVAL, "%s: mean_probs_out must be 16-byte aligned", who);
+// mean_probs_out of the multi-entry heads needs the output to have the size the probabilities are
+// averaged at: avg_h x avg_w, "the <avg_name> size" in the message.
+static int check_mean_probs_out(seg_ctx* c, const char* who, const float* mean_probs_out, int out_h,
+                                int out_w, const char* avg_name, int avg_h, int avg_w) {
   if (mean_probs_out && (out_h != avg_h || out_w != avg_w))
     return set_err(&c->err, -EINVAL, "%s: mean_probs_out needs the output size %dx%d to be the "
                    "%s size %dx%d", who, out_h, out_w, avg_name, avg_h, avg_w);
-  return 0;
+  return check_aligned16(c, who, mean_probs_out, "mean_probs_out");
 }
 
 int seg_predict(seg_ctx* c, const int32_t* cid_map, int n_map, int replace_voids, int out_h,
@@ -219,18 +232,13 @@ int seg_predict(seg_ctx* c, const int32_t* cid_map, int n_map, int replace_voids
   NEED_BOUND(c);
   if (int r = join_stem(c, (hipStream_t)stream)) return r;
   const seg_cfg& g = c->cfg;
-  if (!cid_map || !decisions_out) return set_err(&c->err, -EINVAL, "null cid_map / decisions_out");
-  if (n_map != c->tables.n_pp)
-    return set_err(&c->err, -EINVAL, "cid map has %d entries, the model has %d training classes",
-                   n_map, c->tables.n_pp);
-  if (out_h < 1 || out_w < 1) return set_err(&c->err, -EINVAL, "bad output size %dx%d", out_h, out_w);
-  if (replace_voids < 0 || replace_voids > 2)
-    return set_err(&c->err, -EINVAL, "replace_voids = %d (0, 1 or 2)", replace_voids);
   EvalArgs a{};
+  if (int r = check_decision_args(c, nullptr, 2, "", replace_voids, cid_map, n_map, out_h, out_w,
+                                  decisions_out, a.map))
+    return r;
   a.logits = c->head_in; a.N = c->logits.N; a.Hl = c->logits.H; a.Wl = c->logits.W;
   a.ldl = c->ldl; a.H = g.height; a.W = g.width; a.Ho = out_h; a.Wo = out_w;
   a.replace_voids = replace_voids; a.n_map = n_map; a.out = decisions_out;
-  if (int r = normalise_cid_map(c, nullptr, cid_map, n_map, a.map)) return r;
   HIPCALL(c, launch_eval_decisions(a, c->tables, (hipStream_t)stream));
   return 0;
 }
@@ -244,8 +252,8 @@ int seg_full_predictions(seg_ctx* c, float* logits_out, float* probs_out,
   a.ldl = c->ldl; a.H = c->cfg.height; a.W = c->cfg.width;
   a.logits_out = logits_out; a.probs_out = probs_out;
   a.head_decs_out = head_decisions_out; a.decs_out = decisions_out;
-  if ((reinterpret_cast<uintptr_t>(logits_out) | reinterpret_cast<uintptr_t>(probs_out)) & 15)
-    return set_err(&c->err, -EINVAL, "logits_out / probs_out must be 16-byte aligned");
+  if (int r = check_aligned16(c, nullptr, logits_out, "logits_out")) return r;
+  if (int r = check_aligned16(c, nullptr, probs_out, "probs_out")) return r;
   HIPCALL(c, launch_full_predictions(a, c->tables, (hipStream_t)stream));
   return 0;
 }
@@ -255,18 +263,19 @@ int seg_tta_decisions(seg_ctx* c, const seg_tta_entry* entries, int n_entries,
                       float* mean_probs_out, int32_t* decisions_out, void* stream) {
   const char* who = "seg_tta_decisions";
   if (!c) return set_err(nullptr, -EINVAL, "%s: null ctx", who);
-  if (!entries || !cid_map || !decisions_out)
-    return set_err(&c->err, -EINVAL, "%s: null entries / cid_map / decisions_out", who);
+  if (!entries) return set_err(&c->err, -EINVAL, "%s: null entries", who);
   if (n_entries < 1 || n_entries > SEG_TTA_MAX_ENTRIES)
     return set_err(&c->err, -EINVAL, "%s: %d entries (1..%d)", who, n_entries, SEG_TTA_MAX_ENTRIES);
   static_assert(SEG_TTA_MAX_ENTRIES == TTA_MAX_ENTRIES, "entry table size");
   const seg_cfg& g = c->cfg;
   const LossTables& t = c->tables;
   const int ct = t.c1 + t.c2 + t.c3;
-  if (int r = check_averaged_head(c, who, replace_voids, n_map, out_h, out_w, mean_probs_out, "network",
-                                  g.height, g.width))
-    return r;
   TtaArgs a{};
+  if (int r = check_decision_args(c, who, 1, "averaged", replace_voids, cid_map, n_map, out_h, out_w,
+                                  decisions_out, a.map))
+    return r;
+  if (int r = check_mean_probs_out(c, who, mean_probs_out, out_h, out_w, "network", g.height, g.width))
+    return r;
   for (int i = 0; i < n_entries; ++i) {
     const seg_tta_entry& e = entries[i];
     if (!e.logits) return set_err(&c->err, -EINVAL, "%s: entry %d: null logits", who, i);
@@ -283,7 +292,6 @@ int seg_tta_decisions(seg_ctx* c, const seg_tta_entry* entries, int n_entries,
   a.N = c->logits.N; a.H = g.height; a.W = g.width; a.Ho = out_h; a.Wo = out_w;
   a.replace_voids = replace_voids; a.n_map = n_map;
   a.probs = mean_probs_out; a.out = decisions_out;
-  if (int r = normalise_cid_map(c, who, cid_map, n_map, a.map)) return r;
   HIPCALL(c, launch_tta_decisions(a, t, (hipStream_t)stream));
   return 0;
 }
@@ -295,8 +303,7 @@ int seg_window_decisions(seg_ctx* c, const float* const* logits, int h_low, int 
                          float* mean_probs_out, int32_t* decisions_out, void* stream) {
   const char* who = "seg_window_decisions";
   if (!c) return set_err(nullptr, -EINVAL, "%s: null ctx", who);
-  if (!logits || !ys || !xs || !cid_map || !decisions_out)
-    return set_err(&c->err, -EINVAL, "%s: null logits / ys / xs / cid_map / decisions_out", who);
+  if (!logits || !ys || !xs) return set_err(&c->err, -EINVAL, "%s: null logits / ys / xs", who);
   if (ny < 1 || nx < 1)
     return set_err(&c->err, -EINVAL, "%s: %d x %d windows (at least 1 x 1)", who, ny, nx);
   if (flip < 0 || flip > 1) return set_err(&c->err, -EINVAL, "%s: flip = %d (0 or 1)", who, flip);
@@ -333,10 +340,12 @@ int seg_window_decisions(seg_ctx* c, const float* const* logits, int h_low, int 
   };
   if (int rc = origins("ys", ys, ny, g.height, canvas_h)) return rc;
   if (int rc = origins("xs", xs, nx, g.width, canvas_w)) return rc;
-  if (int r = check_averaged_head(c, who, replace_voids, n_map, out_h, out_w, mean_probs_out, "canvas",
-                                  canvas_h, canvas_w))
-    return r;
   WinArgs a{};
+  if (int r = check_decision_args(c, who, 1, "averaged", replace_voids, cid_map, n_map, out_h, out_w,
+                                  decisions_out, a.map))
+    return r;
+  if (int r = check_mean_probs_out(c, who, mean_probs_out, out_h, out_w, "canvas", canvas_h, canvas_w))
+    return r;
   for (int i = 0; i < (int)n_entries; ++i) {
     if (!logits[i]) return set_err(&c->err, -EINVAL, "%s: entry %d: null logits", who, i);
     a.logits[i] = logits[i];
@@ -350,7 +359,6 @@ int seg_window_decisions(seg_ctx* c, const float* const* logits, int h_low, int 
   a.Ho = out_h; a.Wo = out_w;
   a.replace_voids = replace_voids; a.n_map = n_map;
   a.probs = mean_probs_out; a.out = decisions_out;
-  if (int r = normalise_cid_map(c, who, cid_map, n_map, a.map)) return r;
   HIPCALL(c, launch_window_decisions(a, t, (hipStream_t)stream));
   return 0;
 }
@@ -378,8 +386,6 @@ int seg_crf_decisions(seg_ctx* c, const float* probs, const float* images, int n
   if (!probs) return set_err(err, -EINVAL, "%s: null probs", who);
   if (!images) return set_err(err, -EINVAL, "%s: null images", who);
   if (!p) return set_err(err, -EINVAL, "%s: null params (seg_crf_params)", who);
-  if (!cid_map) return set_err(err, -EINVAL, "%s: null cid_map", who);
-  if (!decisions_out) return set_err(err, -EINVAL, "%s: null decisions_out", who);
   if (n < 1 || H < 1 || W < 1)
     return set_err(err, -EINVAL, "%s: bad size n = %d, H = %d, W = %d", who, n, H, W);
   if (p->iterations < 0 || p->iterations > CRF_MAX_ITERATIONS)
@@ -400,32 +406,21 @@ int seg_crf_decisions(seg_ctx* c, const float* probs, const float* images, int n
   }
   const LossTables& t = c->tables;
   const int ct = t.c1 + t.c2 + t.c3;
-  if (replace_voids == 2)
-    return set_err(err, -EINVAL, "%s: replace_voids = 2 (the PREDICT order on resized "
-                   "probabilities) is not defined for refined probabilities; use 1", who);
-  if (replace_voids < 0 || replace_voids > 1)
-    return set_err(err, -EINVAL, "%s: replace_voids = %d (0 or 1)", who, replace_voids);
-  if (n_map != t.n_pp)
-    return set_err(err, -EINVAL, "%s: cid_map has %d entries, the model has %d training classes",
-                   who, n_map, t.n_pp);
-  if (out_h < 1 || out_w < 1)
-    return set_err(err, -EINVAL, "%s: bad output size out_h x out_w = %dx%d", who, out_h, out_w);
-  if (reinterpret_cast<uintptr_t>(probs) & 15)
-    return set_err(err, -EINVAL, "%s: probs must be 16-byte aligned", who);
-  if (reinterpret_cast<uintptr_t>(probs_out) & 15)
-    return set_err(err, -EINVAL, "%s: probs_out must be 16-byte aligned", who);
+  CrfDecideArgs da{};
+  if (int r = check_decision_args(c, who, 1, "refined", replace_voids, cid_map, n_map, out_h, out_w,
+                                  decisions_out, da.map))
+    return r;
+  if (int r = check_aligned16(c, who, probs, "probs")) return r;
+  if (int r = check_aligned16(c, who, probs_out, "probs_out")) return r;
   const int T = p->iterations;
   const int64_t buf = crf_buffer_bytes(n, H, W, ct);
   if (T >= 1) {
     if (!workspace) return set_err(err, -EINVAL, "%s: null workspace with iterations = %d", who, T);
-    if (reinterpret_cast<uintptr_t>(workspace) & 15)
-      return set_err(err, -EINVAL, "%s: workspace must be 16-byte aligned", who);
+    if (int r = check_aligned16(c, who, workspace, "workspace")) return r;
     if (workspace_bytes < 2 * buf)
       return set_err(err, -EINVAL, "%s: workspace of %lld bytes, %lld needed (seg_crf_workspace)",
                      who, (long long)workspace_bytes, (long long)(2 * buf));
   }
-  CrfDecideArgs da{};
-  if (int r = normalise_cid_map(c, who, cid_map, n_map, da.map)) return r;
 
   hipStream_t s = (hipStream_t)stream;
   const float* q = probs;   // Q^0 = P

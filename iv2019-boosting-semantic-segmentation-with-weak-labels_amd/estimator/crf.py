@@ -20,7 +20,7 @@ from __future__ import annotations
 import math
 from collections import namedtuple
 
-from estimator.tta import HEAD_LAYOUT
+from estimator.inference import cached_driver
 
 MAX_ITERATIONS, MAX_RADIUS, MAX_DILATION = 32, 5, 4   # the limits of seg_crf_decisions
 DEFAULT_ITERATIONS = 5   # the published setting; the flag itself defaults to 0 = off
@@ -113,7 +113,6 @@ class CRFDriver(object):
         from seg_hip import CrfParams
         self.ctx = ctx
         self.settings = settings
-        self.widths, self.n_pp = HEAD_LAYOUT[ctx.cfg.dataset]
         self.params = CrfParams(*settings)
         self._buffers = {}
 
@@ -122,7 +121,7 @@ class CRFDriver(object):
         from seg_hip import crf_workspace_bytes
         key = (n, H, W)
         if key not in self._buffers:
-            nbytes = crf_workspace_bytes(n, H, W, sum(self.widths))
+            nbytes = crf_workspace_bytes(n, H, W, sum(self.ctx.head_widths))
             self._buffers[key] = torch.empty(nbytes, dtype=torch.uint8, device=self.ctx.device)
         return self._buffers[key]
 
@@ -143,50 +142,4 @@ def driver_for_crf(ctx, params):
     """The context's CRF driver for these settings (built on first use, kept on the context), or
     None when the settings ask for no refinement."""
     st = crf_settings(params)
-    if st is None:
-        return None
-    cache = ctx.__dict__.setdefault('_crf_drivers', {})
-    if st not in cache:
-        cache[st] = CRFDriver(ctx, st)
-    return cache[st]
-
-
-def refine_decisions(crf, predictions, proimages, cid_map, decs, replace_voids, win=None, tta=None):
-    """The decisions of a batch under ``--crf_iterations``: the probabilities of the active path
-    -- the window driver's canvas means, the TTA driver's means, or ``probs_out`` of
-    ``seg_full_predictions`` for the one forward ``model_fn`` ran -- refined by ``crf`` on
-    ``proimages`` and decided into ``decs``. The predictions' lazy ``*_probabilities`` /
-    ``*_decisions`` then come from Q^T."""
-    import torch
-    ctx = crf.ctx
-    if win is not None:
-        from estimator.windows import attach_window_predictions
-        ents = win.entries(proimages)
-        probs = win.mean_probabilities(ents)
-        attach_window_predictions(predictions, win, ents)
-    elif tta is not None:
-        from estimator.tta import attach_predictions
-        ents = tta.entries(proimages)
-        probs = tta.mean_probabilities(ents)
-        attach_predictions(predictions, tta, ents)
-    else:
-        n = int(proimages.shape[0])
-        probs = torch.empty((n, ctx.cfg.height, ctx.cfg.width, sum(crf.widths)),
-                            dtype=torch.float32, device=ctx.device)
-        ctx.full_predictions(probs=probs)
-    q = torch.empty_like(probs)
-    crf.decisions(probs, proimages, cid_map, decs, replace_voids, probs_out=q)
-    predictions.use_refined(lambda: refined_materialise(q, crf.widths))
-
-
-def refined_materialise(probs, widths):
-    """The lazy ``*_probabilities`` (per-head slices of the refined probabilities) and
-    ``*_decisions`` (their argmax) entries of the model's predictions."""
-    import torch
-    from models.resnet50_extended_model_hierarchical import HEADS
-    out, lo = {}, 0
-    for head, ci in zip(HEADS, widths):
-        out[f'{head}_probabilities'] = probs[..., lo:lo + ci]
-        out[f'{head}_decisions'] = torch.argmax(probs[..., lo:lo + ci], dim=-1).to(torch.int32)
-        lo += ci
-    return out
+    return cached_driver(ctx, '_crf_drivers', st, lambda: CRFDriver(ctx, st))

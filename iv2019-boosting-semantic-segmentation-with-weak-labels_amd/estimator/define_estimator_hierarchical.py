@@ -148,11 +148,10 @@ def _eval_spec(predictions, labels, config, params, proimages=None):
     params.window_canvas from the probabilities averaged over the windows of the canvas that
     proimages then is (estimator/windows.py, seg_window_decisions). With params.crf_iterations > 0
     the probabilities of whichever of the three paths is active are refined by the mean-field CRF
-    on proimages before the argmax (estimator/crf.py, seg_crf_decisions)."""
+    on proimages before the argmax (estimator/crf.py, seg_crf_decisions). estimator/inference.py
+    picks among them."""
     import torch
-    from estimator.crf import driver_for_crf, refine_decisions
-    from estimator.tta import attach_predictions, driver_for
-    from estimator.windows import attach_window_predictions, driver_for_windows
+    from estimator.inference import decide_batch
     from utils.utils import _replacevoids
     if getattr(params, 'preserve_aspect_ratio', False):
         raise NotImplementedError('evaluation with preserving aspect ratio is not implemented.')
@@ -162,18 +161,7 @@ def _eval_spec(predictions, labels, config, params, proimages=None):
     tcids2ecids = list(params.training_cids2evaluation_cids)
     decs = torch.empty(prolabels.shape, dtype=torch.int32, device=prolabels.device)
     replace = bool(getattr(params, 'replace_voids', False))
-    win = driver_for_windows(ctx, config, params, ModeKeys.EVAL)
-    tta = None if win is not None else driver_for(ctx, config, params, ModeKeys.EVAL)
-    crf = driver_for_crf(ctx, params)
-    if crf is not None:   # --crf_iterations: the active path's probabilities, refined
-        refine_decisions(crf, predictions, proimages, tcids2ecids, decs, replace, win, tta)
-    elif win is not None:   # --window_canvas: proimages is the canvas, every window a forward
-        attach_window_predictions(predictions, win,
-                                  win.decisions(proimages, tcids2ecids, decs, replace))
-    elif tta is None:
-        ctx.predict(tcids2ecids, decs, replace_voids=replace)
-    else:
-        attach_predictions(predictions, tta, tta.decisions(proimages, tcids2ecids, decs, replace))
+    decide_batch(predictions, proimages, ctx, config, params, ModeKeys.EVAL, tcids2ecids, decs, replace)
     nc = max(_replacevoids(tcids2ecids)) + 1
     cm = torch.empty((nc, nc), dtype=torch.int32, device=prolabels.device)
     ctx.confusion(prolabels.to(torch.int32).contiguous(), decs, nc, cm)
@@ -199,9 +187,7 @@ def _predict_spec(predictions, features, params, config=None):
     refined by the mean-field CRF on the prepared images first (estimator/crf.py);
     --replace_voids then also replaces before the resize (mode 1)."""
     import torch
-    from estimator.crf import driver_for_crf, refine_decisions
-    from estimator.tta import attach_predictions, driver_for
-    from estimator.windows import attach_window_predictions, driver_for_windows
+    from estimator.inference import decide_batch
     ctx = predictions['_context']
     img = features['proimages']
     n, h_net, w_net = img.shape[0], img.shape[1], img.shape[2]
@@ -211,20 +197,8 @@ def _predict_spec(predictions, features, params, config=None):
         size = (int(raw.shape[1]), int(raw.shape[2])) if raw is not None else (h_net, w_net)
     replace = bool(getattr(params, 'replace_voids', False))
     decs = torch.empty((n,) + tuple(size), dtype=torch.int32, device=img.device)
-    win = driver_for_windows(ctx, config, params, ModeKeys.PREDICT)
-    tta = None if win is not None else driver_for(ctx, config, params, ModeKeys.PREDICT)
-    crf = driver_for_crf(ctx, params)
-    if crf is not None:   # --crf_iterations: the active path's probabilities, refined
-        refine_decisions(crf, predictions, img, list(range(params.output_Nclasses)), decs, replace,
-                         win, tta)
-    elif win is not None:   # --window_canvas: img is the canvas, every window a forward
-        attach_window_predictions(predictions, win,
-                                  win.decisions(img, list(range(params.output_Nclasses)), decs, replace))
-    elif tta is None:
-        ctx.predict(list(range(params.output_Nclasses)), decs, replace_voids=replace, order="predict")
-    else:
-        attach_predictions(predictions, tta,
-                           tta.decisions(img, list(range(params.output_Nclasses)), decs, replace))
+    decide_batch(predictions, img, ctx, config, params, ModeKeys.PREDICT,
+                 list(range(params.output_Nclasses)), decs, replace, order="predict")
     out = predictions
     out['decisions'] = decs
     for k in ('rawimages', 'rawimagespaths'):

@@ -16,9 +16,12 @@ from __future__ import annotations
 import copy
 import math
 
+from estimator.inference import Source, cached_driver
+
 MAX_ENTRIES = 16   # SEG_TTA_MAX_ENTRIES: scales x (1 + flip) of one decision launch
-# seg_cfg.dataset (0 cityscapes, 1 vistas) -> (head widths l1 | l2 vehicle | l2 human, training classes)
-HEAD_LAYOUT = {0: ((14, 7, 3), 20), 1: ((53, 12, 5), 66)}
+NO_LOGITS = ('test-time augmentation (--tta_scales / --tta_flip) averages probabilities over several '
+             'forwards; there are no full-resolution logits of the average (the *_probabilities '
+             'entries hold it)')
 
 
 def add_tta_arguments(argparser):
@@ -65,8 +68,9 @@ def tta_sizes(H, W, scales):
     return sizes
 
 
-class TTADriver(object):
-    """The scale contexts of one primary context and the per-batch entry loop.
+class TTADriver(Source):
+    """The scale contexts of one primary context and the per-batch entry loop (a source of
+    ``estimator.inference``; the mean probabilities live at the network size).
 
     ``primary`` is the context ``model_fn`` runs (the network size H x W). One context per other
     size comes from ``get_context`` (so ``release_contexts()`` frees them), must lay its
@@ -74,13 +78,14 @@ class TTADriver(object):
     ``moving`` buffers copied whenever the primary's parameters were (re)loaded
     (``SegContext.params_version``; ``--eval_all_ckpts`` restores inside its loop)."""
 
+    no_logits = NO_LOGITS
+
     def __init__(self, primary, config, params, mode, scales, flip):
         self.primary = primary
         self.scales = tuple(scales)
         self.flip = bool(flip)
-        self.widths, self.n_pp = HEAD_LAYOUT[primary.cfg.dataset]
-        H, W = primary.cfg.height, primary.cfg.width
-        self.sizes = tta_sizes(H, W, self.scales)
+        self.size = (primary.cfg.height, primary.cfg.width)
+        self.sizes = tta_sizes(*self.size, self.scales)
         n_entries = len(self.sizes) * (2 if self.flip else 1)
         if n_entries > MAX_ENTRIES:
             raise ValueError(f'test-time augmentation: {len(self.sizes)} scales'
@@ -120,11 +125,11 @@ class TTADriver(object):
             ctx.set_bn_inference(infer)
         self._synced = (p.params_version, infer)
 
-    def entries(self, proimages, primary_ran=True):
+    def entries(self, proimages):
         """One forward per entry on ``proimages`` (device f32 [N, H, W, 3] in [-1, 1)); returns
         [(low-resolution logits, flip)] in entry order. The logits are clones: the flipped run of
-        a context overwrites its unflipped logits. ``primary_ran``: the primary context's last
-        forward was on ``proimages`` (``model_fn`` has run), so its unflipped entry is there.
+        a context overwrites its unflipped logits. The primary context's last forward was on
+        ``proimages`` (``model_fn`` has run), so its unflipped entry is there already.
         Afterwards a context's own state (``outputs()``, ``predict``, ``full_predictions``) is
         that of the last entry it ran: with flip, the primary's is the mirrored image's."""
         from seg_hip import resize_images
@@ -136,17 +141,15 @@ class TTADriver(object):
         for ctx in self.contexts:
             h, w = ctx.cfg.height, ctx.cfg.width
             for flip in ((False, True) if self.flip else (False,)):
-                if not (ctx is p and not flip and primary_ran):
-                    # the scale-1.0 unflipped entry is proimages itself, without a copy
-                    ctx.forward(x if (ctx is p and not flip) else resize_images(x, h, w, flip))
+                if not (ctx is p and not flip):   # the primary's unflipped forward is model_fn's
+                    ctx.forward(resize_images(x, h, w, flip))
                 out.append((ctx.outputs()[2].clone(), flip))
         return out
 
-    def decisions(self, proimages, cid_map, out, replace_voids=False, primary_ran=True):
-        """Decisions of the batch into ``out`` (device int32 [N, Ho, Wo]); returns the entries."""
-        ents = self.entries(proimages, primary_ran)
-        self.primary.tta_decisions(ents, cid_map, out, replace_voids=replace_voids)
-        return ents
+    def decide(self, entries, cid_map, out, replace_voids=False, mean_probs=None):
+        """One ``seg_tta_decisions`` launch over ``entries`` into ``out`` (device int32 [N, Ho, Wo])."""
+        self.primary.tta_decisions(entries, cid_map, out, replace_voids=replace_voids,
+                                   mean_probs=mean_probs)
 
     def primary_entry(self):
         """Index of the primary context's unflipped entry, or None when no scale runs at the
@@ -155,62 +158,27 @@ class TTADriver(object):
             return None
         return self.contexts.index(self.primary) * (2 if self.flip else 1)
 
-    def mean_probabilities(self, entries):
-        """Mean probabilities f32 [N, H, W, c1 + c2 + c3] of ``entries`` at the network size. This
-        launches the decision head over all entries a second time (the decisions path keeps no
-        full-resolution tensor), which is the price of asking for them."""
-        import torch
-        p = self.primary
-        n = entries[0][0].shape[0]
-        probs = torch.empty((n, p.cfg.height, p.cfg.width, sum(self.widths)), dtype=torch.float32,
-                            device=p.device)
-        decs = torch.empty((n, p.cfg.height, p.cfg.width), dtype=torch.int32, device=p.device)
-        p.tta_decisions(entries, list(range(self.n_pp)), decs, mean_probs=probs)
-        return probs
+    def attach(self, predictions, entries, refined=None):
+        """Under test-time augmentation the model's lazy full-resolution entries come from the
+        averaged probabilities (or ``refined``): ``*_probabilities`` are slices of them,
+        ``*_decisions`` their per-head argmax, and ``*_logits`` do not exist.
+
+        The eager ``*_logits_lowres`` entries are views of the primary context's output buffer, which
+        the primary's mirrored forward has overwritten when flip is on: they are replaced by slices
+        of the clone of its unflipped logits, so they keep describing ``proimages`` itself."""
+        from models.resnet50_extended_model_hierarchical import HEADS
+        i = self.primary_entry()
+        if i is not None:
+            lo = 0
+            for head, ci in zip(HEADS, self.primary.head_widths):
+                predictions[f'{head}_logits_lowres'] = entries[i][0][..., lo:lo + ci]
+                lo += ci
+        super().attach(predictions, entries, refined)
 
 
 def driver_for(ctx, config, params, mode):
     """The primary context's driver for these settings (built on first use, kept on the
     context), or None when the settings ask for no test-time augmentation."""
     st = tta_settings(params)
-    if st is None:
-        return None
-    key = (st, mode)
-    cache = ctx.__dict__.setdefault('_tta_drivers', {})
-    if key not in cache:
-        cache[key] = TTADriver(ctx, config, params, mode, *st)
-    return cache[key]
-
-
-def attach_predictions(predictions, driver, entries):
-    """Under test-time augmentation the model's lazy full-resolution entries come from the
-    averaged probabilities: ``*_probabilities`` are slices of the mean probabilities,
-    ``*_decisions`` their per-head argmax, and ``*_logits`` do not exist. Materialising them
-    runs the decision head once more over all entries (``TTADriver.mean_probabilities``).
-
-    The eager ``*_logits_lowres`` entries are views of the primary context's output buffer, which
-    the primary's mirrored forward has overwritten when flip is on: they are replaced by slices
-    of the clone of its unflipped logits, so they keep describing ``proimages`` itself."""
-    from models.resnet50_extended_model_hierarchical import HEADS
-    i = driver.primary_entry()
-    if i is not None:
-        lo = 0
-        for head, ci in zip(HEADS, driver.widths):
-            predictions[f'{head}_logits_lowres'] = entries[i][0][..., lo:lo + ci]
-            lo += ci
-
-    predictions.use_tta(lambda: materialise(driver, entries))
-
-
-def materialise(driver, entries):
-    """The lazy ``*_probabilities`` (per-head slices of ``driver.mean_probabilities(entries)``) and
-    ``*_decisions`` (their argmax) of a TTADriver or a WindowDriver."""
-    import torch
-    from models.resnet50_extended_model_hierarchical import HEADS
-    probs = driver.mean_probabilities(entries)
-    out, lo = {}, 0
-    for head, ci in zip(HEADS, driver.widths):
-        out[f'{head}_probabilities'] = probs[..., lo:lo + ci]
-        out[f'{head}_decisions'] = torch.argmax(probs[..., lo:lo + ci], dim=-1).to(torch.int32)
-        lo += ci
-    return out
+    return cached_driver(ctx, '_tta_drivers', st and (st, mode),
+                         lambda: TTADriver(ctx, config, params, mode, *st))

@@ -15,7 +15,7 @@ where they are used.
 """
 from __future__ import annotations
 
-from estimator.tta import HEAD_LAYOUT, materialise
+from estimator.inference import Source, cached_driver
 
 MAX_ENTRIES = 64   # SEG_WIN_MAX_ENTRIES: windows x (1 + flip) of one decision launch
 
@@ -93,16 +93,18 @@ def input_size(params):
     return st[0]
 
 
-class WindowDriver(object):
-    """The window grid of one primary context and the per-batch entry loop: every entry is a
-    forward of ``primary`` itself on one window of the canvas."""
+class WindowDriver(Source):
+    """The window grid of one primary context and the per-batch entry loop (a source of
+    ``estimator.inference``; the mean probabilities live at the canvas size): every entry is a
+    forward of ``primary`` itself on one window of the canvas. Neither ``*_logits`` nor
+    ``*_logits_lowres`` exist in the predictions (no single forward saw the canvas): the model's
+    ``Predictions`` of a canvas say so from the start."""
 
     def __init__(self, primary, canvas, stride, flip):
         self.primary = primary
-        self.canvas = (int(canvas[0]), int(canvas[1]))
+        self.canvas = self.size = (int(canvas[0]), int(canvas[1]))
         self.stride = (int(stride[0]), int(stride[1]))
         self.flip = bool(flip)
-        self.widths, self.n_pp = HEAD_LAYOUT[primary.cfg.dataset]
         self.net = (primary.cfg.height, primary.cfg.width)
         self.ys, self.xs = window_grid(self.canvas, self.net, self.stride, self.flip)
 
@@ -129,46 +131,15 @@ class WindowDriver(object):
             out.append(p.outputs()[2].clone())
         return out
 
-    def decisions(self, proimages, cid_map, out, replace_voids=False):
-        """Decisions of the batch into ``out`` (device int32 [N, Ho, Wo]); returns the entries."""
-        ents = self.entries(proimages)
-        self.primary.window_decisions(ents, self.ys, self.xs, self.flip, self.canvas, cid_map, out,
-                                      replace_voids=replace_voids)
-        return ents
-
-    def mean_probabilities(self, entries):
-        """Mean probabilities f32 [N, Hc, Wc, c1 + c2 + c3] of ``entries`` at the canvas size. This
-        launches the decision head over all entries a second time (the decisions path keeps no
-        full-resolution tensor), which is the price of asking for them."""
-        import torch
-        p = self.primary
-        n = entries[0].shape[0]
-        probs = torch.empty((n,) + self.canvas + (sum(self.widths),), dtype=torch.float32,
-                            device=p.device)
-        decs = torch.empty((n,) + self.canvas, dtype=torch.int32, device=p.device)
-        p.window_decisions(entries, self.ys, self.xs, self.flip, self.canvas,
-                           list(range(self.n_pp)), decs, mean_probs=probs)
-        return probs
+    def decide(self, entries, cid_map, out, replace_voids=False, mean_probs=None):
+        """One ``seg_window_decisions`` launch over ``entries`` into ``out`` (device int32
+        [N, Ho, Wo])."""
+        self.primary.window_decisions(entries, self.ys, self.xs, self.flip, self.canvas, cid_map, out,
+                                      replace_voids=replace_voids, mean_probs=mean_probs)
 
 
 def driver_for_windows(ctx, config, params, mode):
     """The primary context's window driver for these settings (built on first use, kept on the
     context), or None when the settings ask for no sliding windows."""
     st = window_settings(params)
-    if st is None:
-        return None
-    key = (st, mode)
-    cache = ctx.__dict__.setdefault('_window_drivers', {})
-    if key not in cache:
-        cache[key] = WindowDriver(ctx, *st)
-    return cache[key]
-
-
-def attach_window_predictions(predictions, driver, entries):
-    """Under sliding windows the model's lazy full-resolution entries come from the mean
-    probabilities at the canvas size: ``*_probabilities`` are slices of them, ``*_decisions``
-    their per-head argmax, and neither ``*_logits`` nor ``*_logits_lowres`` exist (no single
-    forward saw the canvas). Materialising runs the decision head once more over all entries
-    (``WindowDriver.mean_probabilities``)."""
-    # the same lazy-entry hook; the windows' KeyError is the model's
-    predictions.use_tta(lambda: materialise(driver, entries))
+    return cached_driver(ctx, '_window_drivers', st and (st, mode), lambda: WindowDriver(ctx, *st))

@@ -137,6 +137,9 @@ def model(mode, features, labels, config, params):
 
 HEADS = ('l1', 'l2_vehicle', 'l2_human')
 LAZY_KEYS = tuple(f'{h}_{k}' for h in HEADS for k in ('logits', 'probabilities', 'decisions'))
+NO_CANVAS_LOGITS = ('sliding windows (--window_canvas) average probabilities over the windows that '
+                    'cover a pixel; no forward saw the canvas, so there are no logits of it (the '
+                    '*_probabilities entries hold the average)')
 
 
 class Predictions(MutableMapping):
@@ -159,18 +162,22 @@ class Predictions(MutableMapping):
 
     def __init__(self, ctx, dataset='cityscapes', canvas=None):
         import torch
+        from seg_hip import HEAD_LAYOUT
         self._ctx = ctx
         self._forward_id = getattr(ctx, 'forward_count', 0)
-        self._c = (53, 12, 5) if dataset == 'vistas' else (14, 7, 3)
-        self._tta = None   # set by use_tta
-        self._refined = None   # set by use_refined
-        self._refined_entries = None
-        self._windows = canvas is not None   # sliding windows: (n, Hc, Wc), no forward has run
-        if self._windows:
+        self._c = HEAD_LAYOUT[dataset][0]
+        # a lazy key -> the callable whose dict holds it (replace_lazy); the keys that do not
+        # exist, and why
+        self._lazy, self._absent, self._why = {}, set(), None
+        if canvas is not None:   # sliding windows: (n, Hc, Wc), no forward has run
             self._shape = tuple(int(v) for v in canvas)
             self._store = {'decisions': torch.zeros(self._shape, dtype=torch.int32, device=ctx.device),
                            '_context': ctx}
+            # until the window driver attaches the means there is nothing behind the lazy keys
+            self._absent = {f'{h}_{k}' for h in HEADS for k in ('logits', 'logits_lowres')}
+            self._why = NO_CANVAS_LOGITS
             return
+        self._lazy = dict.fromkeys(LAZY_KEYS, self._materialise)
         _, _, logits = ctx.outputs()
         n, h, w = logits.shape[0], ctx.cfg.height, ctx.cfg.width
         self._shape = (n, h, w)
@@ -193,49 +200,34 @@ class Predictions(MutableMapping):
         probs = torch.empty_like(logits)
         hd = torch.empty((n, h, w, 3), dtype=torch.int32, device=dev)
         self._ctx.full_predictions(logits, probs, hd)
-        lo = 0
+        out, lo = {}, 0
         for i, (head, c) in enumerate(zip(HEADS, self._c)):
-            self._store[f'{head}_logits'] = logits[..., lo:lo + c]
-            self._store[f'{head}_probabilities'] = probs[..., lo:lo + c]
-            self._store[f'{head}_decisions'] = hd[..., i]
+            out[f'{head}_logits'] = logits[..., lo:lo + c]
+            out[f'{head}_probabilities'] = probs[..., lo:lo + c]
+            out[f'{head}_decisions'] = hd[..., i]
             lo += c
+        return out
 
-    def use_tta(self, materialise):
-        """Test-time augmentation (estimator/tta.py): the lazy entries come from the averaged
-        probabilities. ``materialise()`` returns the ``*_probabilities`` / ``*_decisions``
-        entries; averaged logits do not exist, so ``*_logits`` raise KeyError and are not
-        listed by iteration. Sliding windows (estimator/windows.py) use the same hook with the
-        mean probabilities at the canvas size."""
-        self._tta = materialise
-
-    def use_refined(self, entries):
-        """CRF refinement (estimator/crf.py): ``entries()`` returns the ``*_probabilities`` /
-        ``*_decisions`` of the refined probabilities Q^T, which then stand in for the model's (or
-        the averaged) ones; the ``*_logits`` entries are untouched."""
-        self._refined = entries
-        self._refined_entries = None
+    def replace_lazy(self, keys, produce, absent=(), why=None):
+        """The one hook of the inference sources and the CRF (estimator/inference.py): the lazy
+        ``keys`` now come from ``produce()``, a dict holding them that is asked for when one of them
+        is first read; the ``absent`` keys do not exist: reading one raises KeyError with ``why``,
+        and iteration does not list them. Keys not named keep what stood behind them, so a
+        refinement that replaces ``*_probabilities`` / ``*_decisions`` leaves ``*_logits`` alone."""
+        for k in keys:
+            self._store.pop(k, None)
+            self._lazy[k] = produce
+        if absent:
+            self._absent, self._why = self._absent | set(absent), why
 
     def __getitem__(self, k):
-        if self._refined is not None and k in LAZY_KEYS and not k.endswith('_logits'):
-            if self._refined_entries is None:
-                self._refined_entries = self._refined()
-            return self._refined_entries[k]
-        if self._windows and k not in self._store and (
-                k in LAZY_KEYS or k.endswith('_logits_lowres')):
-            if k.endswith('_logits') or k.endswith('_logits_lowres') or self._tta is None:
-                raise KeyError(f'{k}: sliding windows (--window_canvas) average probabilities over '
-                               'the windows that cover a pixel; no forward saw the canvas, so there '
-                               'are no logits of it (the *_probabilities entries hold the average)')
-            self._store.update(self._tta())
-        if k in LAZY_KEYS and k not in self._store:
-            if self._tta is None:
-                self._materialise()
-            elif k.endswith('_logits'):
-                raise KeyError(f'{k}: test-time augmentation (--tta_scales / --tta_flip) averages '
-                               'probabilities over several forwards; there are no full-resolution '
-                               'logits of the average (the *_probabilities entries hold it)')
-            else:
-                self._store.update(self._tta())
+        if k not in self._store:
+            produce = self._lazy.get(k)
+            if k in self._absent or (k in LAZY_KEYS and produce is None):
+                raise KeyError(f'{k}: {self._why}')
+            if produce is not None:   # its other entries may have been replaced since
+                self._store.update((kk, v) for kk, v in produce().items()
+                                   if self._lazy.get(kk) is produce)
         return self._store[k]
 
     def __setitem__(self, k, v):
@@ -245,9 +237,7 @@ class Predictions(MutableMapping):
         del self._store[k]
 
     def _lazy_keys(self):
-        if self._tta is None and not self._windows:
-            return LAZY_KEYS
-        return tuple(k for k in LAZY_KEYS if not k.endswith('_logits'))
+        return tuple(k for k in LAZY_KEYS if k not in self._absent)
 
     def __iter__(self):
         return iter(list(dict.fromkeys(self._lazy_keys() + tuple(self._store))))
@@ -257,7 +247,7 @@ class Predictions(MutableMapping):
 
     def materialised(self):
         """The entries computed so far (no launch): a plain dict."""
-        return dict(self._store, **(self._refined_entries or {}))
+        return dict(self._store)
 
 
 def add_model_arguments(argparser):

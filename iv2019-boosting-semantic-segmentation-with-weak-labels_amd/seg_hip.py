@@ -47,6 +47,8 @@ SEG_ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void
 PYRAMID = {"none": 0, "psp": 1, "aspp": 2}
 DTYPE = {"fp32": 0, "bf16": 1, "fp16": 2}
 DATASET = {"cityscapes": 0, "vistas": 1}
+# dataset -> (head widths l1 | l2 vehicle | l2 human, training classes)
+HEAD_LAYOUT = {"cityscapes": ((14, 7, 3), 20), "vistas": ((53, 12, 5), 66)}
 PARAM_KIND = {0: "weights", 1: "gamma", 2: "beta", 3: "moving_mean", 4: "moving_variance",
               5: "biases"}
 UPSAMPLING = {"bilinear": 0, "hybrid": 1}
@@ -234,6 +236,16 @@ def crf_workspace_bytes(n: int, H: int, W: int, ct: int) -> int:
     return b.value
 
 
+def _check_tensor(t, dtype, rank, n, name, tail=()):
+    """``t`` must be a contiguous device tensor of ``dtype`` and ``rank`` whose leading dimension is
+    ``n`` (None: any) and whose last dimensions are ``tail``; ``name`` is what the message calls it."""
+    if not (t.dtype == dtype and t.is_cuda and t.is_contiguous() and t.dim() == rank
+            and (n is None or t.shape[0] == n) and tuple(t.shape[rank - len(tail):]) == tuple(tail)):
+        dims = ["n" if n is None else str(n)] + ["*"] * (rank - 1 - len(tail)) + [str(v) for v in tail]
+        raise ValueError(f"{name} must be a contiguous device {str(dtype).split('.')[-1]} "
+                         f"[{', '.join(dims)}], got {tuple(t.shape)} {t.dtype}")
+
+
 def _ptr(t) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
@@ -272,6 +284,8 @@ class SegContext:
                           bn_decay, int(bool(train_bn)), weight_decay, fov_k, fov_rate,
                           UPSAMPLING[upsampling], NORM[norm], groups)
         self.dtype = dtype
+        self.head_widths, self.n_classes = HEAD_LAYOUT[dataset]
+        self.batch_size = nb_pp + nb_pb + nb_pi
         h = ctypes.c_void_p()
         check(LIB.seg_create(self.device.index, ctypes.byref(self.cfg), ctypes.byref(h)))
         self.h = h
@@ -362,19 +376,15 @@ class SegContext:
         check(LIB.seg_set_bn_inference(self.h, 1 if on else 0), self.h)
         self.bn_inference = bool(on)
 
-    def _decision_args(self, cid_map, out, mean_probs=None, hw="H, W"):
+    def _decision_args(self, cid_map, out, mean_probs=None, n=None):
         """(batch size, cid_map as a C array) after the checks the decision calls share: ``out`` a
-        contiguous device int32 [N, Ho, Wo], ``mean_probs`` None or a contiguous device float32
-        [N, ``hw``, C]."""
+        contiguous device int32 [n, Ho, Wo], ``mean_probs`` None or a contiguous device float32
+        [n, H, W, C]. ``n``: the batch size when it is not the context's."""
         import torch
-        n = self.cfg.nb_pp + self.cfg.nb_pb + self.cfg.nb_pi
-        if not (out.dtype == torch.int32 and out.dim() == 3 and out.is_contiguous()
-                and out.shape[0] == n and out.is_cuda):
-            raise ValueError(f"decisions buffer must be a contiguous device int32 [{n}, Ho, Wo]")
-        if mean_probs is not None and not (mean_probs.dtype == torch.float32 and mean_probs.is_cuda
-                                           and mean_probs.is_contiguous() and mean_probs.dim() == 4
-                                           and mean_probs.shape[0] == n):
-            raise ValueError(f"mean_probs must be a contiguous device float32 [{n}, {hw}, C]")
+        n = self.batch_size if n is None else n
+        _check_tensor(out, torch.int32, 3, n, "decisions buffer")
+        if mean_probs is not None:
+            _check_tensor(mean_probs, torch.float32, 4, n, "mean_probs")
         return n, (ctypes.c_int32 * len(cid_map))(*[int(v) for v in cid_map])
 
     def predict(self, cid_map, out, replace_voids=False, stream=None, order="eval"):
@@ -399,19 +409,12 @@ class SegContext:
         logits / probs f32 [N, H, W, C] (C = c1 + c2 + c3, heads l1 | l2v | l2h),
         head_decisions int32 [N, H, W, 3], decisions int32 [N, H, W] (fused, common cids)."""
         import torch
-        n = self.cfg.nb_pp + self.cfg.nb_pb + self.cfg.nb_pi
-        hw = (self.cfg.height, self.cfg.width)
-        for t, dt, tail in ((logits, torch.float32, None), (probs, torch.float32, None),
-                            (head_decisions, torch.int32, (3,)), (decisions, torch.int32, ())):
-            if t is None:
-                continue
-            if tail is None:
-                tail = (sum((53, 12, 5) if self.cfg.dataset == DATASET["vistas"] else (14, 7, 3)),)
-            ok = (t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape[:3]) == (n,) + hw
-                  and tuple(t.shape[3:]) == tail)
-            if not ok:
-                raise ValueError(f"prediction buffer {tuple(t.shape)} {t.dtype}: expected a "
-                                 f"contiguous device tensor [{n}, {hw[0]}, {hw[1]}, ...]")
+        hw, ct = (self.cfg.height, self.cfg.width), (sum(self.head_widths),)
+        for name, t, dt, tail in (("logits", logits, torch.float32, ct), ("probs", probs, torch.float32, ct),
+                                  ("head_decisions", head_decisions, torch.int32, (3,)),
+                                  ("decisions", decisions, torch.int32, ())):
+            if t is not None:
+                _check_tensor(t, dt, 3 + len(tail), self.batch_size, name, hw + tail)
         check(LIB.seg_full_predictions(self.h, _ptr(logits), _ptr(probs), _ptr(head_decisions),
                                        _ptr(decisions), _stream(stream)), self.h)
 
@@ -431,10 +434,7 @@ class SegContext:
                              "(scales x flips) per decision launch")
         arr = (TtaEntry * max(len(entries), 1))()
         for i, (lg, flip) in enumerate(entries):
-            if not (lg.dtype == torch.float32 and lg.is_cuda and lg.is_contiguous()
-                    and lg.dim() == 4 and lg.shape[0] == n):
-                raise ValueError(f"entry {i}: logits must be a contiguous device float32 "
-                                 f"[{n}, h_low, w_low, ld], got {tuple(lg.shape)} {lg.dtype}")
+            _check_tensor(lg, torch.float32, 4, n, f"entry {i}: logits")
             arr[i] = TtaEntry(lg.data_ptr(), int(lg.shape[1]), int(lg.shape[2]), int(lg.shape[3]),
                               int(flip))
         check(LIB.seg_tta_decisions(self.h, arr, len(entries), m, len(cid_map), int(replace_voids),
@@ -453,7 +453,7 @@ class SegContext:
         [N, Hc, Wc, c1 + c2 + c3]; needs out's size to be the canvas size. The context's own
         logits are not read."""
         import torch
-        n, m = self._decision_args(cid_map, out, mean_probs, "Hc, Wc")
+        n, m = self._decision_args(cid_map, out, mean_probs)
         ys, xs = [int(v) for v in ys], [int(v) for v in xs]
         want = len(ys) * len(xs) * (2 if flip else 1)
         if want > WIN_MAX_ENTRIES:
@@ -463,12 +463,8 @@ class SegContext:
             raise ValueError(f"{len(entries)} entries for {len(ys)} x {len(xs)} windows"
                              f"{' with flip' if flip else ''}: expected {want} (at least 1)")
         shape = tuple(entries[0].shape)
-        for i, lg in enumerate(entries):
-            if not (lg.dtype == torch.float32 and lg.is_cuda and lg.is_contiguous()
-                    and lg.dim() == 4 and lg.shape[0] == n and tuple(lg.shape) == shape):
-                raise ValueError(f"entry {i}: logits must be a contiguous device float32 "
-                                 f"[{n}, h_low, w_low, ld] of the first entry's shape {shape}, "
-                                 f"got {tuple(lg.shape)} {lg.dtype}")
+        for i, lg in enumerate(entries):   # all of the first entry's shape
+            _check_tensor(lg, torch.float32, 4, n, f"entry {i}: logits", shape[1:])
         ptrs = (_VP * want)(*[lg.data_ptr() for lg in entries])
         check(LIB.seg_window_decisions(self.h, ptrs, shape[1], shape[2], shape[3],
                                        (_INT * len(ys))(*ys), len(ys), (_INT * len(xs))(*xs), len(xs),
@@ -489,22 +485,14 @@ class SegContext:
         caller owns it). ``probs_out``: optional device f32 of probs' shape for the refined
         probabilities Q^T."""
         import torch
-        ok = lambda t, c: (t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.dim() == 4
-                           and (c is None or t.shape[3] == c))
-        if not ok(probs, None):
-            raise ValueError("probs must be a contiguous device float32 [n, H, W, c1 + c2 + c3]")
+        _check_tensor(probs, torch.float32, 4, None, "probs")
         n, H, W, ct = (int(v) for v in probs.shape)
-        if not (ok(images, 3) and tuple(images.shape[:3]) == (n, H, W)):
-            raise ValueError(f"images must be a contiguous device float32 [{n}, {H}, {W}, 3], got "
-                             f"{tuple(images.shape)} {images.dtype}")
-        if not (out.dtype == torch.int32 and out.dim() == 3 and out.is_contiguous()
-                and out.shape[0] == n and out.is_cuda):
-            raise ValueError(f"decisions buffer must be a contiguous device int32 [{n}, Ho, Wo]")
-        if probs_out is not None and not (ok(probs_out, ct) and probs_out.shape == probs.shape):
-            raise ValueError(f"probs_out must be a contiguous device float32 {tuple(probs.shape)}")
+        _check_tensor(images, torch.float32, 4, n, "images", (H, W, 3))
+        _, m = self._decision_args(cid_map, out, n=n)
+        if probs_out is not None:
+            _check_tensor(probs_out, torch.float32, 4, n, "probs_out", (H, W, ct))
         if workspace is not None and not (workspace.is_cuda and workspace.is_contiguous()):
             raise ValueError("workspace must be a contiguous device buffer")
-        m = (ctypes.c_int32 * len(cid_map))(*[int(v) for v in cid_map])
         ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
         check(LIB.seg_crf_decisions(self.h, _ptr(probs), _ptr(images), n, H, W, ctypes.byref(crf),
                                     _ptr(workspace), ws_bytes, m, len(cid_map), int(replace_voids),
@@ -613,7 +601,7 @@ class SegContext:
         ld, hl, wl = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         check(LIB.seg_outputs(self.h, ctypes.byref(l), ctypes.byref(r), ctypes.byref(lg),
                               ctypes.byref(ld), ctypes.byref(hl), ctypes.byref(wl)), self.h)
-        n = self.cfg.nb_pp + self.cfg.nb_pb + self.cfg.nb_pi
+        n = self.batch_size
         return (_wrap(l.value, (10,), self.device), _wrap(r.value, (1,), self.device),
                 _wrap(lg.value, (n, hl.value, wl.value, ld.value), self.device))
 
@@ -701,10 +689,7 @@ def resize_images(x, h: int, w: int, flip: bool = False, stream=None):
     legacy bilinear resize (align_corners = False) of the image, mirrored in x first when
     ``flip``. Equal sizes copy (or mirror) bit for bit."""
     import torch
-    if not (x.dtype == torch.float32 and x.is_cuda and x.is_contiguous() and x.dim() == 4
-            and x.shape[3] == 3):
-        raise ValueError(f"images must be a contiguous device float32 [n, H, W, 3], got "
-                         f"{tuple(x.shape)} {x.dtype}")
+    _check_tensor(x, torch.float32, 4, None, "images", (3,))
     out = torch.empty((x.shape[0], int(h), int(w), 3), dtype=torch.float32, device=x.device)
     check(LIB.seg_resize_images(_ptr(x), int(x.shape[0]), int(x.shape[1]), int(x.shape[2]), int(h),
                                 int(w), int(flip), _ptr(out), _stream(stream)))
@@ -715,10 +700,7 @@ def window_images(x, y0: int, x0: int, H: int, W: int, flip: bool = False, strea
     """seg_window_images: the H x W window at (y0, x0) of a contiguous device float32 canvas
     [n, Hc, Wc, 3], mirrored in x when ``flip``: a bitwise copy [n, H, W, 3]."""
     import torch
-    if not (x.dtype == torch.float32 and x.is_cuda and x.is_contiguous() and x.dim() == 4
-            and x.shape[3] == 3):
-        raise ValueError(f"images must be a contiguous device float32 [n, Hc, Wc, 3], got "
-                         f"{tuple(x.shape)} {x.dtype}")
+    _check_tensor(x, torch.float32, 4, None, "images", (3,))
     if int(H) < 1 or int(W) < 1:
         raise ValueError(f"window size {H} x {W} must be positive")
     out = torch.empty((x.shape[0], int(H), int(W), 3), dtype=torch.float32, device=x.device)

@@ -11,6 +11,9 @@ kernel, the decision kernel, the host driver and the evaluate.py / predict.py fl
 * geometry: a 5 x 3 image at r * d = 20, and N = 2 at 64 x 128 with image 1 from another seed.
 * every refusal of the C entry, with decisions_out unwritten.
 * evaluate.py / predict.py with --crf_iterations alone, with --tta_flip and with --window_canvas.
+* estimator.inference.decide_batch, the one path of both specs, for {one forward, TTA, windows} x
+  {CRF off, on} x {EVAL, PREDICT}: decisions bitwise those of the same low-level calls made by
+  hand, the same number of forwards, the lazy predictions' key sets and KeyError texts.
 """
 import ctypes
 import errno
@@ -405,3 +408,128 @@ def test_lazy_predictions_reflect_the_refined_probabilities(cuda, crf_calls):
     drv = driver_for_crf(ctx, s)
     assert drv is driver_for_crf(ctx, s) and list(drv._buffers) == [(2, 64, 128)]
     release_contexts()
+
+
+# ---- the one decide path: source x refinement x mode ---------------------------------------------
+
+SOURCES = {
+    # extra settings, (height, width) of the prepared batch, forwards beyond model_fn's
+    "single": ({}, (64, 128), 0),
+    "tta": (dict(tta_scales=[0.75, 1.0], tta_flip=True), (64, 128), 3),      # 48 x 96 and 64 x 128, flipped
+    "windows": (dict(window_canvas=[64, 200], window_stride=[24, 40]), (64, 200), 3),   # xs 0, 40, 72
+}
+NO_TTA_LOGITS = ("l1_logits: test-time augmentation (--tta_scales / --tta_flip) averages probabilities "
+                 "over several forwards; there are no full-resolution logits of the average (the "
+                 "*_probabilities entries hold it)")
+NO_WINDOW_LOGITS = ("{}: sliding windows (--window_canvas) average probabilities over the windows that "
+                    "cover a pixel; no forward saw the canvas, so there are no logits of it (the "
+                    "*_probabilities entries hold the average)")
+
+
+@pytest.fixture(scope="module")
+def shared_contexts():
+    """The cases below share the cached contexts (and their drivers): released before and after."""
+    from models.resnet50_extended_model_hierarchical import release_contexts
+    release_contexts()
+    yield
+    release_contexts()
+
+
+@pytest.mark.parametrize("mode", ["EVAL", "PREDICT"])
+@pytest.mark.parametrize("crf", [0, 2])
+@pytest.mark.parametrize("source", sorted(SOURCES))
+def test_decide_batch_is_the_low_level_sequence_bitwise(cuda, shared_contexts, source, crf, mode):
+    """estimator.inference.decide_batch against the same sequence of low-level calls made here, for
+    every source, with and without the CRF (T = 2, r = 1), in both modes, with and without
+    replace_voids: bitwise equal decisions, the same number of forwards, and the lazy predictions'
+    key set and KeyError texts of each mode."""
+    import argparse
+    from estimator.crf import crf_settings
+    from estimator.inference import decide_batch
+    from estimator.mode_keys import ModeKeys
+    from estimator.tta import driver_for
+    from estimator.windows import driver_for_windows
+    from input_pipelines.synthetic import batch
+    from inference_common import _realistic_moving_stats
+    from models.resnet50_extended_model_hierarchical import LAZY_KEYS, get_context, model
+    from seg_hip import CrfParams, crf_workspace_bytes, resize_images, window_images
+    extra, hw, forwards = SOURCES[source]
+    s = argparse.Namespace(Nb=2, height_feature_extractor=64, width_feature_extractor=128,
+                           per_pixel_dataset_name="cityscapes", compute_dtype="fp32", pyramid="psp",
+                           name_feature_extractor="resnet_v1_50", init_seed=3, crf_iterations=crf,
+                           crf_radius=1, **extra)
+    mode = getattr(ModeKeys, mode)
+    order = "predict" if mode == ModeKeys.PREDICT else "eval"
+    cid_map = list(range(20)) if mode == ModeKeys.PREDICT else MAPS["merge"]
+    ctx = get_context(None, s, mode=mode)
+    if not getattr(ctx, "_realistic", False):     # once per context: logits of a trained range
+        _realistic_moving_stats(ctx, torch.as_tensor(batch(99, 2, 0, 0, 64, 128)["images"]).to(cuda))
+        ctx._realistic = True
+    x = torch.as_tensor(batch(12, 2, 0, 0, *hw)["images"]).to(cuda)
+    tta, win = driver_for(ctx, None, s, mode) if source == "tta" else None, driver_for_windows(ctx, None, s, mode)
+    assert (tta is not None, win is not None) == (source == "tta", source == "windows")
+    contexts = {id(c): c for c in [ctx] + (tta.contexts if tta else [])}.values()
+    count = lambda: sum(getattr(c, "forward_count", 0) for c in contexts)
+    lazy = [k for k in LAZY_KEYS if source == "single" or not k.endswith("_logits")]
+    lowres = [] if source == "windows" else [f"{h}_logits_lowres" for h in ("l1", "l2_vehicle", "l2_human")]
+    for rv in (False, True):
+        _, _, pred = model(mode, x, None, None, s)
+        before = count()
+        got = torch.full((2, 45, 77), -9, dtype=torch.int32, device=cuda)
+        decide_batch(pred, x, ctx, None, s, mode, cid_map, got, rv, order=order)
+        print(f"{source} crf {crf} {order} rv {rv}: {count() - before} forwards")
+        assert count() - before == forwards
+        # the lazy predictions
+        assert set(pred.materialised()) == set(["decisions", "_context"] + lowres)     # no launch so far
+        assert set(pred) == set(lazy + lowres + ["decisions", "_context"])
+        if source == "single":
+            assert tuple(pred["l1_logits"].shape) == (2, 64, 128, 14)
+        else:
+            with pytest.raises(KeyError) as e:
+                pred["l1_logits"]
+            assert e.value.args[0] == (NO_TTA_LOGITS if source == "tta" else NO_WINDOW_LOGITS.format("l1_logits"))
+        if source == "windows":
+            with pytest.raises(KeyError) as e:
+                pred["l2_human_logits_lowres"]
+            assert e.value.args[0] == NO_WINDOW_LOGITS.format("l2_human_logits_lowres")
+        lazy_probs = torch.cat([pred[f"{h}_probabilities"] for h in ("l1", "l2_vehicle", "l2_human")], -1)
+        assert tuple(lazy_probs.shape) == (2,) + hw + (24,)
+        # the same sequence of low-level calls, as the specs made them before there was one path
+        model(mode, x, None, None, s)
+        want = torch.full((2, 45, 77), -7, dtype=torch.int32, device=cuda)
+        probs = torch.full((2,) + hw + (24,), -1.0, device=cuda) if crf else None
+        at_size = torch.empty((2,) + hw, dtype=torch.int32, device=cuda)
+        if source == "single":
+            if crf:
+                ctx.full_predictions(probs=probs)
+            else:
+                ctx.predict(cid_map, want, replace_voids=rv, order=order)
+        elif source == "tta":
+            ents = []
+            for c in tta.contexts:
+                for flip in (False, True):
+                    if c is not ctx or flip:
+                        c.forward(resize_images(x, c.cfg.height, c.cfg.width, flip))
+                    ents.append((c.outputs()[2].clone(), flip))
+            if crf:
+                ctx.tta_decisions(ents, list(range(20)), at_size, mean_probs=probs)
+            else:
+                ctx.tta_decisions(ents, cid_map, want, replace_voids=rv)
+        else:
+            ents = []
+            for x0 in (0, 40, 72):
+                ctx.forward(window_images(x, 0, x0, 64, 128, False))
+                ents.append(ctx.outputs()[2].clone())
+            if crf:
+                ctx.window_decisions(ents, [0], [0, 40, 72], False, (64, 200), list(range(20)), at_size,
+                                     mean_probs=probs)
+            else:
+                ctx.window_decisions(ents, [0], [0, 40, 72], False, (64, 200), cid_map, want, replace_voids=rv)
+        if crf:
+            q = torch.full_like(probs, -2.0)
+            ws = torch.empty(crf_workspace_bytes(2, hw[0], hw[1], 24), dtype=torch.uint8, device=cuda)
+            ctx.crf_decisions(probs, x, CrfParams(*crf_settings(s)), cid_map, want, replace_voids=rv,
+                              workspace=ws, probs_out=q)
+            assert torch.equal(lazy_probs, q)       # the lazy probabilities are Q^T
+        assert int(want.min()) >= 0 and len(torch.unique(want)) > 1
+        assert torch.equal(got, want)

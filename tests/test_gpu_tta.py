@@ -294,9 +294,8 @@ def test_driver_scale_contexts_and_decisions(cuda, dtype):
     assert mism <= 1e-3
     # the lazy predictions under test-time augmentation
     from models.resnet50_extended_model_hierarchical import Predictions
-    from estimator.tta import attach_predictions
     pred = Predictions(primary, "cityscapes")
-    attach_predictions(pred, drv, ents)
+    drv.attach(pred, ents)
     p1 = pred["l1_probabilities"]
     assert tuple(p1.shape) == (2, 64, 128, 14)
     np.testing.assert_allclose(p1.sum(-1).cpu().numpy(), 1.0, atol=1e-5)

@@ -365,7 +365,7 @@ def test_driver_entries_and_decisions(cuda, dtype):
     are bitwise those of the context's forward on that window alone, and the driver's decisions
     are the reference's on those native logits (teacher-forced)."""
     from estimator.mode_keys import ModeKeys
-    from estimator.windows import attach_window_predictions, driver_for_windows
+    from estimator.windows import driver_for_windows
     from input_pipelines.synthetic import batch
     from models.resnet50_extended_model_hierarchical import (Predictions, get_context, model,
                                                             release_contexts)
@@ -401,7 +401,7 @@ def test_driver_entries_and_decisions(cuda, dtype):
     # the lazy predictions under sliding windows
     with pytest.raises(KeyError, match="sliding windows"):
         pred["l1_probabilities"]                       # nothing attached yet
-    attach_window_predictions(pred, drv, ents)
+    drv.attach(pred, ents)
     lo = 0
     for head, c in zip(("l1", "l2_vehicle", "l2_human"), (14, 7, 3)):
         p = pred[f"{head}_probabilities"]
