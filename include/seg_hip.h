@@ -367,6 +367,71 @@ int seg_crf_decisions(seg_ctx* ctx, const float* probs, const float* images,
                       int out_h, int out_w,
                       float* probs_out, int32_t* decisions_out, void* stream);
 
+/* box-constrained pseudo-labels: per-head probabilities plus the box list of a weakly labelled
+ * image become per-pixel training labels (no reference counterpart; the semantics are fixed here).
+ * Notation: t = ctx's head tables: c1, c2, c3, cid_l1_vehicle, cid_l1_human, pb2veh[15],
+ *   pb2hum[15], l1_to_common, veh_to_common, hum_to_common, n_pp. The void channel of a head is its
+ *   last channel. IGNORE = n_pp - 1, the void training cid (19 Cityscapes, 65 Vistas). CT = c1 +
+ *   c2 + c3, channels l1 | l2 vehicle | l2 human as for seg_crf_decisions.
+ * Box kinds: a box of weak class k (0..13) is a vehicle box if pb2veh[k] != c2 - 1, a human box if
+ *   pb2hum[k] != c3 - 1, inert otherwise (classes 11..13 in both datasets).
+ * Cover: boxes, cids, box_off, geom and max_boxes are those of seg_bbox_labels (below) without
+ *   flip, and so is the mapping: rectangles are (int)((double)coord * size) at the source size;
+ *   pixel (y, x) of the H x W map has the source pixel
+ *   min((int)floorf((float)(y + oy) * ((float)src_h / (float)rh)), src_h - 1), likewise in x;
+ *   inclusion is >= min && <= max on both axes. Pixel i is covered by box b if its source pixel
+ *   lies in b's rectangle. mask_i has bit k set if some box of class k covers i.
+ *   AV_i = { pb2veh[k] : bit k set, vehicle box }, AH_i likewise with pb2hum for human boxes.
+ * n, H, W are each call's own, as for seg_crf_decisions; only the tables come from ctx. All
+ *   pointers are device memory.
+ *
+ * seg_box_constrain: probs = P, fp32 [n][H][W][CT] -> probs_out = P', same layout, not P. The l1
+ *   channels are copied bit for bit. Vehicle head: AV_i empty: copied bit for bit. Otherwise the
+ *   channels outside AV_i become +0.0f (the void channel included), s = the fp32 sum of the kept
+ *   channels in channel order, and the kept channels become P(c) * (1.f / s); if !(s >= 1e-30f)
+ *   the head is copied unchanged (the CRF's rule). Human head: the same with AH_i. mask_out:
+ *   optional (NULL skips it) uint16 [n][H][W] = mask_i. seg_crf_decisions multiplies its message
+ *   into the unary, so a zero of P' stays zero through every mean-field step: constrain first,
+ *   refine second.
+ * seg_box_decisions: q = Q, fp32 [n][H][W][CT] (P', or probs_out of seg_crf_decisions run on P')
+ *   -> labels_out int32 [n][H][W], training cids at the size of the probabilities. d1 = the
+ *   first-maximum argmax of the l1 values, conf = Q_l1[d1]. d1 == cid_l1_vehicle: IGNORE if AV_i
+ *   is empty (a vehicle with no box behind it), else veh_to_common[d2], d2 the first maximum over
+ *   the channels of AV_i only, in channel order. d1 == cid_l1_human: the same with AH_i and
+ *   hum_to_common. Any other d1: l1_to_common[d1]. If !(conf >= tau) the label is IGNORE.
+ *   conf_out: optional fp32 [n][H][W]. counts_out: int32 [total_boxes][2] = (area_b, hit_b):
+ *   area_b the pixels of its image covered by b; hit_b those of them whose label equals
+ *   veh_to_common[pb2veh[k]] for a vehicle box of class k, hum_to_common[pb2hum[k]] for a human
+ *   box, 0 for an inert box. The entry zeroes counts_out itself, on the stream; the sums are
+ *   integers, exact in any order.
+ * seg_box_finalize: labels int32 [n][H][W], reject int32 [total_boxes] -> out int32
+ *   [n][out_h][out_w]: every output pixel takes the label of its NEAREST_NEIGHBOR align_corners
+ *   source pixel (as the decision entries resize) and becomes IGNORE if any box with
+ *   reject[b] != 0 covers that source pixel. The caller forms reject on the host: 1 if b is a
+ *   vehicle or human box (seg_box_kinds), area_b > 0 and hit_b < min_fill * area_b in float64; inert
+ *   boxes and boxes of zero area are never rejected.
+ * -EINVAL with a seg_last_error text naming the function and the parameter, no launch and the
+ *   outputs unwritten, for: a null ctx, probs / q / labels, boxes, cids, box_off, geom, probs_out,
+ *   labels_out, counts_out, reject or out; n, H, W or an output size < 1 (n above 65535);
+ *   max_boxes outside 0..1024; probs, q or probs_out not 16-byte aligned; probs_out == probs; tau
+ *   not finite or outside [0, 1]. Head widths other than the two datasets' are an error. Class ids
+ *   outside 0..13 and a geom whose crop leaves the resized map are the caller's to refuse. */
+/* seg_box_kinds: the kind of every weak class under ctx's head tables, host int32 kinds[14]:
+ *   1 vehicle box, 2 human box, 0 inert -- what the host's reject rule needs to know. Host-only. */
+int seg_box_kinds(seg_ctx* ctx, int32_t* kinds);
+int seg_box_constrain(seg_ctx* ctx, const float* probs, int n, int H, int W,
+                      const float* boxes, const int32_t* cids, const int32_t* box_off,
+                      const int32_t* geom, int max_boxes,
+                      float* probs_out, uint16_t* mask_out, void* stream);
+int seg_box_decisions(seg_ctx* ctx, const float* q, int n, int H, int W,
+                      const float* boxes, const int32_t* cids, const int32_t* box_off,
+                      const int32_t* geom, int max_boxes, float tau,
+                      int32_t* labels_out, float* conf_out, int32_t* counts_out, void* stream);
+int seg_box_finalize(seg_ctx* ctx, const int32_t* labels, int n, int H, int W,
+                     const float* boxes, const int32_t* cids, const int32_t* box_off,
+                     const int32_t* geom, int max_boxes, const int32_t* reject,
+                     int out_h, int out_w, int32_t* out, void* stream);
+
 /* input preprocessing (input_cityscapes.py:66-96,190-209), after the host
  * decodes TFRecord -> tf.train.Example -> PNG (input_pipelines/tfrecords.py):
  * seg_prepare_images: raw uint8 [n][src_h][src_w][3] -> convert_image_dtype -> bilinear

@@ -458,6 +458,90 @@ int seg_crf_decisions(seg_ctx* c, const float* probs, const float* images, int n
   return 0;
 }
 
+// What the three box-label entries (seg_box_constrain, seg_box_decisions, seg_box_finalize) ask of
+// the context, the size and the box lists; fills b.
+static int check_box_args(seg_ctx* c, const char* who, int n, int H, int W, const float* boxes,
+                          const int32_t* cids, const int32_t* box_off, const int32_t* geom,
+                          int max_boxes, BoxListArgs* b) {
+  if (!c) return set_err(nullptr, -EINVAL, "%s: null ctx", who);
+  std::string* err = &c->err;
+  if (!boxes) return set_err(err, -EINVAL, "%s: null boxes", who);
+  if (!cids) return set_err(err, -EINVAL, "%s: null cids", who);
+  if (!box_off) return set_err(err, -EINVAL, "%s: null box_off", who);
+  if (!geom) return set_err(err, -EINVAL, "%s: null geom", who);
+  if (n < 1 || n > 65535 || H < 1 || W < 1)
+    return set_err(err, -EINVAL, "%s: bad size n = %d, H = %d, W = %d", who, n, H, W);
+  if (max_boxes < 0 || max_boxes > BOXLABEL_MAX_BOXES)
+    return set_err(err, -EINVAL, "%s: max_boxes = %d (0..%d boxes per image)", who, max_boxes,
+                   BOXLABEL_MAX_BOXES);
+  static_assert(sizeof(BboxGeom) == 6 * sizeof(int32_t), "geom layout");
+  *b = BoxListArgs{boxes, cids, box_off, reinterpret_cast<const BboxGeom*>(geom)};
+  return 0;
+}
+
+int seg_box_kinds(seg_ctx* c, int32_t* kinds) {
+  const char* who = "seg_box_kinds";
+  if (!c) return set_err(nullptr, -EINVAL, "%s: null ctx", who);
+  if (!kinds) return set_err(&c->err, -EINVAL, "%s: null kinds", who);
+  const LossTables& t = c->tables;
+  for (int k = 0; k < SEG_WEAK_CLASSES - 1; ++k)
+    kinds[k] = t.pb2veh[k] != t.c2 - 1 ? 1 : t.pb2hum[k] != t.c3 - 1 ? 2 : 0;
+  return 0;
+}
+
+int seg_box_constrain(seg_ctx* c, const float* probs, int n, int H, int W, const float* boxes,
+                      const int32_t* cids, const int32_t* box_off, const int32_t* geom,
+                      int max_boxes, float* probs_out, uint16_t* mask_out, void* stream) {
+  const char* who = "seg_box_constrain";
+  BoxConstrainArgs a{};
+  if (int r = check_box_args(c, who, n, H, W, boxes, cids, box_off, geom, max_boxes, &a.b)) return r;
+  if (!probs) return set_err(&c->err, -EINVAL, "%s: null probs", who);
+  if (!probs_out) return set_err(&c->err, -EINVAL, "%s: null probs_out", who);
+  if (int r = check_aligned16(c, who, probs, "probs")) return r;
+  if (int r = check_aligned16(c, who, probs_out, "probs_out")) return r;
+  if (probs_out == probs) return set_err(&c->err, -EINVAL, "%s: probs_out must not be probs", who);
+  a.p = probs; a.N = n; a.H = H; a.W = W; a.out = probs_out; a.mask = mask_out;
+  HIPCALL(c, launch_box_constrain(a, c->tables, (hipStream_t)stream));
+  return 0;
+}
+
+int seg_box_decisions(seg_ctx* c, const float* q, int n, int H, int W, const float* boxes,
+                      const int32_t* cids, const int32_t* box_off, const int32_t* geom,
+                      int max_boxes, float tau, int32_t* labels_out, float* conf_out,
+                      int32_t* counts_out, void* stream) {
+  const char* who = "seg_box_decisions";
+  BoxDecideArgs a{};
+  if (int r = check_box_args(c, who, n, H, W, boxes, cids, box_off, geom, max_boxes, &a.b)) return r;
+  if (!q) return set_err(&c->err, -EINVAL, "%s: null q", who);
+  if (!labels_out) return set_err(&c->err, -EINVAL, "%s: null labels_out", who);
+  if (!counts_out) return set_err(&c->err, -EINVAL, "%s: null counts_out", who);
+  if (int r = check_aligned16(c, who, q, "q")) return r;
+  if (!std::isfinite(tau) || tau < 0.f || tau > 1.f)
+    return set_err(&c->err, -EINVAL, "%s: tau = %g (a finite value in [0, 1])", who, (double)tau);
+  a.q = q; a.N = n; a.H = H; a.W = W; a.max_boxes = max_boxes; a.tau = tau;
+  a.labels = labels_out; a.conf = conf_out; a.counts = counts_out;
+  HIPCALL(c, launch_box_decisions(a, c->tables, (hipStream_t)stream));
+  return 0;
+}
+
+int seg_box_finalize(seg_ctx* c, const int32_t* labels, int n, int H, int W, const float* boxes,
+                     const int32_t* cids, const int32_t* box_off, const int32_t* geom,
+                     int max_boxes, const int32_t* reject, int out_h, int out_w, int32_t* out,
+                     void* stream) {
+  const char* who = "seg_box_finalize";
+  BoxFinalizeArgs a{};
+  if (int r = check_box_args(c, who, n, H, W, boxes, cids, box_off, geom, max_boxes, &a.b)) return r;
+  if (!labels) return set_err(&c->err, -EINVAL, "%s: null labels", who);
+  if (!reject) return set_err(&c->err, -EINVAL, "%s: null reject", who);
+  if (!out) return set_err(&c->err, -EINVAL, "%s: null out", who);
+  if (out_h < 1 || out_w < 1)
+    return set_err(&c->err, -EINVAL, "%s: bad output size out_h x out_w = %dx%d", who, out_h, out_w);
+  a.labels = labels; a.reject = reject; a.N = n; a.H = H; a.W = W; a.Ho = out_h; a.Wo = out_w;
+  a.out = out;
+  HIPCALL(c, launch_box_finalize(a, c->tables, (hipStream_t)stream));
+  return 0;
+}
+
 int seg_backward(seg_ctx* c, void* stream) {
   NEED_BOUND(c);
   Step S{c, (hipStream_t)stream, c->dt};

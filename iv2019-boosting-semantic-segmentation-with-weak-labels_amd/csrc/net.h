@@ -16,6 +16,7 @@
 #include "../../include/seg_hip.h"
 #include "bn.h"
 #include "bootstrap.h"
+#include "boxlabel.h"
 #include "lbf.h"
 #include "input.h"
 #include "augment.h"

@@ -185,7 +185,10 @@ def _predict_spec(predictions, features, params, config=None):
     for averaged probabilities). params.window_canvas: the same from the windows of the canvas
     (estimator/windows.py). params.crf_iterations > 0: the probabilities of the active path are
     refined by the mean-field CRF on the prepared images first (estimator/crf.py);
-    --replace_voids then also replaces before the resize (mode 1)."""
+    --replace_voids then also replaces before the resize (mode 1). When the features carry
+    'boxlists' (per image (cids, coords, src_size): pseudo_label.py) the decisions are the
+    box-constrained pseudo-labels of estimator/pseudo.py and 'pseudo_report' their per-image
+    report; --replace_voids does not apply to them."""
     import torch
     from estimator.inference import decide_batch
     ctx = predictions['_context']
@@ -197,11 +200,18 @@ def _predict_spec(predictions, features, params, config=None):
         size = (int(raw.shape[1]), int(raw.shape[2])) if raw is not None else (h_net, w_net)
     replace = bool(getattr(params, 'replace_voids', False))
     decs = torch.empty((n,) + tuple(size), dtype=torch.int32, device=img.device)
-    decide_batch(predictions, img, ctx, config, params, ModeKeys.PREDICT,
-                 list(range(params.output_Nclasses)), decs, replace, order="predict")
+    report = None
+    if 'boxlists' in features:
+        from estimator.pseudo import label_batch
+        _, report = label_batch(predictions, img, features['boxlists'], ctx, config, params, decs)
+    else:
+        decide_batch(predictions, img, ctx, config, params, ModeKeys.PREDICT,
+                     list(range(params.output_Nclasses)), decs, replace, order="predict")
     out = predictions
     out['decisions'] = decs
-    for k in ('rawimages', 'rawimagespaths'):
+    if report is not None:
+        out['pseudo_report'] = report
+    for k in ('rawimages', 'rawimagespaths', 'imageids'):
         if k in features:
             out[k] = features[k]
     return EstimatorSpec(ModeKeys.PREDICT, out, None, None, None)

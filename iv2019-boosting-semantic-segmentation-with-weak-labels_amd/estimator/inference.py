@@ -110,6 +110,15 @@ class ForwardSource(Source):
             super().attach(predictions, entries, refined)
 
 
+def pick_source(ctx, config, params, mode, order='eval'):
+    """The probability source the settings name: ``--window_canvas``, else ``--tta_scales`` /
+    ``--tta_flip``, else the forward ``model_fn`` ran, which alone honours ``order``."""
+    from estimator.tta import driver_for
+    from estimator.windows import driver_for_windows
+    return (driver_for_windows(ctx, config, params, mode) or driver_for(ctx, config, params, mode)
+            or ForwardSource(ctx, order))
+
+
 def decide_batch(predictions, images, ctx, config, params, mode, cid_map, decs, replace_voids,
                  order='eval'):
     """The decisions of the batch ``images`` into ``decs`` (device int32 [N, Ho, Wo]), mapped through
@@ -120,10 +129,7 @@ def decide_batch(predictions, images, ctx, config, params, mode, cid_map, decs, 
     ``predictions`` (the model's, of ``ctx``) get the matching lazy entries."""
     import torch
     from estimator.crf import driver_for_crf
-    from estimator.tta import driver_for
-    from estimator.windows import driver_for_windows
-    source = (driver_for_windows(ctx, config, params, mode) or driver_for(ctx, config, params, mode)
-              or ForwardSource(ctx, order))
+    source = pick_source(ctx, config, params, mode, order)
     crf = driver_for_crf(ctx, params)
     entries = source.entries(images)
     refined = None

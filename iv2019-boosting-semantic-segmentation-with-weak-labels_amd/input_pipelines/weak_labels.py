@@ -74,6 +74,39 @@ def bbox_label_map(cids, coords_normalized, src_size, resized_size, offset, out_
     return np.ascontiguousarray(rla[iy][:, ix])
 
 
+MAX_BOXES_PER_IMAGE = 1024   # what the kernels stage per image (reference MAX_N_BBOXES = 516)
+
+
+def pack_box_lists(images, out_size):
+    """The flat host arrays the box entries of the C ABI read (seg_bbox_labels, seg_box_*), from
+    items (cids, coords (k, 4) = (xmin, xmax, ymin, ymax), src_size, resized_size, offset):
+    boxes f32 [max(total, 1), 4], cids i32 [max(total, 1)], box_off i32 [n + 1], geom i32
+    [max(n, 1), 6] = (src_h, src_w, resized_h, resized_w, crop_y, crop_x), and the per-image
+    counts. Refuses more than 1024 boxes in an image, a crop of ``out_size`` that leaves the
+    resized map and class ids outside [0, 13]."""
+    n = len(images)
+    counts = [len(im[0]) for im in images]
+    if max(counts, default=0) > MAX_BOXES_PER_IMAGE:
+        raise ValueError("at most 1024 boxes per image (reference MAX_N_BBOXES = 516)")
+    for cids, coords, src, rs, off in images:
+        if rs[0] < off[0] + out_size[0] or rs[1] < off[1] + out_size[1]:
+            raise ValueError(f"crop {off} + {tuple(out_size)} outside the resized map {rs}")
+        if len(cids) and (np.min(cids) < 0 or np.max(cids) >= N_WEAK_CLASSES - 1):
+            raise ValueError("box class ids must be in [0, 13]")
+    boxes = np.zeros((max(sum(counts), 1), 4), np.float32)
+    cid = np.zeros(max(sum(counts), 1), np.int32)
+    off = np.zeros(n + 1, np.int32)
+    geom = np.zeros((max(n, 1), 6), np.int32)
+    for i, (cids, coords, src, rs, o) in enumerate(images):
+        k = counts[i]
+        off[i + 1] = off[i] + k
+        if k:
+            boxes[off[i]:off[i + 1]] = np.asarray(coords, np.float32).reshape(k, 4)
+            cid[off[i]:off[i + 1]] = np.asarray(cids, np.int32)
+        geom[i] = (src[0], src[1], rs[0], rs[1], o[0], o[1])
+    return boxes, cid, off, geom, counts
+
+
 class BboxLabelsGPU:
     """Device-side bbox / tag label maps through the C ABI (seg_bbox_labels / seg_tag_labels):
     the [n][H][W][15] tensors the loss head reads are produced on the GPU from box lists."""
@@ -91,25 +124,7 @@ class BboxLabelsGPU:
         n = len(images)
         flips = np.asarray([int(im[5]) if len(im) > 5 else 0 for im in images], np.int32)
         images = [tuple(im[:5]) for im in images]
-        counts = [len(im[0]) for im in images]
-        if max(counts, default=0) > 1024:
-            raise ValueError("at most 1024 boxes per image (reference MAX_N_BBOXES = 516)")
-        for cids, coords, src, rs, off in images:
-            if rs[0] < off[0] + self.h or rs[1] < off[1] + self.w:
-                raise ValueError(f"crop {off} + {(self.h, self.w)} outside the resized map {rs}")
-            if len(cids) and (np.min(cids) < 0 or np.max(cids) >= N_WEAK_CLASSES - 1):
-                raise ValueError("box class ids must be in [0, 13]")
-        boxes = np.zeros((max(sum(counts), 1), 4), np.float32)
-        cid = np.zeros(max(sum(counts), 1), np.int32)
-        off = np.zeros(n + 1, np.int32)
-        geom = np.zeros((max(n, 1), 6), np.int32)
-        for i, (cids, coords, src, rs, o) in enumerate(images):
-            k = counts[i]
-            off[i + 1] = off[i] + k
-            if k:
-                boxes[off[i]:off[i + 1]] = np.asarray(coords, np.float32).reshape(k, 4)
-                cid[off[i]:off[i + 1]] = np.asarray(cids, np.int32)
-            geom[i] = (src[0], src[1], rs[0], rs[1], o[0], o[1])
+        boxes, cid, off, geom, counts = pack_box_lists(images, (self.h, self.w))
         dev = torch.device(self.device)
         tb, tc, to, tg = (torch.as_tensor(x).to(dev) for x in (boxes, cid, off, geom))
         if out is None:

@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = [
     "seg_resize_images", "seg_tta_decisions",
     "seg_window_images", "seg_window_decisions",
     "seg_crf_workspace", "seg_crf_decisions",
+    "seg_box_kinds", "seg_box_constrain", "seg_box_decisions", "seg_box_finalize",
 ]
 
 # int (*seg_allreduce_fn)(void* user, float* buf, int64_t n, void* stream)
@@ -209,6 +210,10 @@ def _load():
         "seg_crf_workspace": (ip, [ip, ip, ip, ip, ctypes.POINTER(i64)]),
         "seg_crf_decisions": (ip, [vp, vp, vp, ip, ip, ip, ctypes.POINTER(CrfParams), vp, i64,
                                    ctypes.POINTER(ctypes.c_int32), ip, ip, ip, ip, vp, vp, vp]),
+        "seg_box_kinds": (ip, [vp, ctypes.POINTER(ctypes.c_int32)]),
+        "seg_box_constrain": (ip, [vp, vp, ip, ip, ip, vp, vp, vp, vp, ip, vp, vp, vp]),
+        "seg_box_decisions": (ip, [vp, vp, ip, ip, ip, vp, vp, vp, vp, ip, f, vp, vp, vp, vp]),
+        "seg_box_finalize": (ip, [vp, vp, ip, ip, ip, vp, vp, vp, vp, ip, vp, ip, ip, vp, vp]),
     }
     override = "SEG_HIP_LIB" in os.environ   # A/B builds of older commits may lack new entries
     for name, (res, args) in sig.items():
@@ -263,6 +268,20 @@ class ParamInfo:
     numel: int
     kind: str
     shape: tuple
+
+
+@dataclass
+class DeviceBoxLists:
+    """A ``BoxLists`` on the device (``SegContext.upload_boxes``): the box arrays of the C ABI,
+    the per-image maximum, the total and the (H, W) of the label maps their geometry is for."""
+    boxes: object
+    cids: object
+    box_off: object
+    geom: object
+    n: int
+    max_boxes: int
+    total: int
+    size: tuple
 
 
 class SegContext:
@@ -498,6 +517,91 @@ class SegContext:
                                     _ptr(workspace), ws_bytes, m, len(cid_map), int(replace_voids),
                                     int(out.shape[1]), int(out.shape[2]), _ptr(probs_out), _ptr(out),
                                     _stream(stream)), self.h)
+
+    def box_kinds(self):
+        """seg_box_kinds: per weak class 0..13, 1 for a vehicle box, 2 for a human box, 0 for an
+        inert one, under this context's head tables."""
+        kinds = (ctypes.c_int32 * 14)()
+        check(LIB.seg_box_kinds(self.h, kinds), self.h)
+        return list(kinds)
+
+    def upload_boxes(self, box_lists, size):
+        """A ``BoxLists`` (items (cids, coords, src_size, resized_size, offset), no flip) on the
+        device, for label maps of ``size`` = (H, W): the ``DeviceBoxLists`` the ``box_*`` calls take.
+        One upload serves every call of a batch."""
+        import torch
+        from input_pipelines.weak_labels import pack_box_lists
+        items = [tuple(im) for im in box_lists]
+        if any(len(im) > 5 and int(im[5]) for im in items):
+            raise ValueError("box labels are not defined for flipped box lists")
+        boxes, cids, off, geom, counts = pack_box_lists([im[:5] for im in items], size)
+        dev = torch.device(self.device)
+        tb, tc, to, tg = (torch.as_tensor(x).to(dev) for x in (boxes, cids, off, geom))
+        return DeviceBoxLists(tb, tc, to, tg, len(items), max(counts, default=0), int(off[-1]),
+                              (int(size[0]), int(size[1])))
+
+    def _boxes_for(self, boxes, n, H, W):
+        b = boxes if isinstance(boxes, DeviceBoxLists) else self.upload_boxes(boxes, (H, W))
+        if b.n != n or b.size != (H, W):
+            raise ValueError(f"box lists of {b.n} images for {b.size[0]}x{b.size[1]} maps, the call "
+                             f"has {n} images of {H}x{W}")
+        return b
+
+    def box_constrain(self, probs, boxes, probs_out, mask_out=None, stream=None):
+        """seg_box_constrain: ``probs`` (contiguous device f32 [n, H, W, c1 + c2 + c3]) with every
+        l2 head restricted to the channels the boxes covering the pixel allow, into ``probs_out``
+        (same shape, not ``probs``). ``boxes``: a ``BoxLists`` or an ``upload_boxes`` result for
+        H x W. ``mask_out``: optional device int16 [n, H, W], bit k = a box of class k covers the
+        pixel. Returns the uploaded boxes."""
+        import torch
+        _check_tensor(probs, torch.float32, 4, None, "probs")
+        n, H, W, ct = (int(v) for v in probs.shape)
+        _check_tensor(probs_out, torch.float32, 4, n, "probs_out", (H, W, ct))
+        if mask_out is not None:
+            _check_tensor(mask_out, torch.int16, 3, n, "mask_out", (H, W))
+        b = self._boxes_for(boxes, n, H, W)
+        check(LIB.seg_box_constrain(self.h, _ptr(probs), n, H, W, _ptr(b.boxes), _ptr(b.cids),
+                                    _ptr(b.box_off), _ptr(b.geom), b.max_boxes, _ptr(probs_out),
+                                    _ptr(mask_out), _stream(stream)), self.h)
+        return b
+
+    def box_decisions(self, q, boxes, tau, labels_out, counts_out, conf_out=None, stream=None):
+        """seg_box_decisions: labels in training cids (device int32 [n, H, W]) from ``q``
+        (contiguous device f32 [n, H, W, c1 + c2 + c3], constrained and possibly refined
+        probabilities), the fine class taken among the channels the covering boxes allow, the void
+        cid for an unboxed vehicle / human pixel or an l1 confidence below ``tau``.
+        ``counts_out``: device int32 [total boxes (at least 1), 2] = (area, hit) per box.
+        ``conf_out``: optional device f32 [n, H, W]. Returns the uploaded boxes."""
+        import torch
+        _check_tensor(q, torch.float32, 4, None, "q")
+        n, H, W, _ = (int(v) for v in q.shape)
+        _check_tensor(labels_out, torch.int32, 3, n, "labels_out", (H, W))
+        if conf_out is not None:
+            _check_tensor(conf_out, torch.float32, 3, n, "conf_out", (H, W))
+        b = self._boxes_for(boxes, n, H, W)
+        _check_tensor(counts_out, torch.int32, 2, max(b.total, 1), "counts_out", (2,))
+        check(LIB.seg_box_decisions(self.h, _ptr(q), n, H, W, _ptr(b.boxes), _ptr(b.cids),
+                                    _ptr(b.box_off), _ptr(b.geom), b.max_boxes, float(tau),
+                                    _ptr(labels_out), _ptr(conf_out), _ptr(counts_out),
+                                    _stream(stream)), self.h)
+        return b
+
+    def box_finalize(self, labels, boxes, reject, out, stream=None):
+        """seg_box_finalize: ``labels`` (device int32 [n, H, W]) nearest-neighbour resized
+        (align_corners) to ``out`` (device int32 [n, Ho, Wo]), the void cid under every box whose
+        entry of ``reject`` (device int32 [total boxes (at least 1)]) is nonzero. Returns the
+        uploaded boxes."""
+        import torch
+        _check_tensor(labels, torch.int32, 3, None, "labels")
+        n, H, W = (int(v) for v in labels.shape)
+        _check_tensor(out, torch.int32, 3, n, "out")
+        b = self._boxes_for(boxes, n, H, W)
+        _check_tensor(reject, torch.int32, 1, max(b.total, 1), "reject")
+        check(LIB.seg_box_finalize(self.h, _ptr(labels), n, H, W, _ptr(b.boxes), _ptr(b.cids),
+                                   _ptr(b.box_off), _ptr(b.geom), b.max_boxes, _ptr(reject),
+                                   int(out.shape[1]), int(out.shape[2]), _ptr(out),
+                                   _stream(stream)), self.h)
+        return b
 
     def backward(self, stream=None):
         check(LIB.seg_backward(self.h, _stream(stream)), self.h)
