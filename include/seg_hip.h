@@ -180,6 +180,52 @@ int seg_outputs(seg_ctx* ctx, const float** losses, const float** reg,
 int seg_confusion(seg_ctx* ctx, const int32_t* labels, const int32_t* decisions, int64_t n,
                   int num_classes, int32_t* cm, void* stream);
 
+/* boundary-band (trimap) confusion: the confusion matrix restricted to the pixels within w pixels
+ * of a ground-truth label boundary, for several w (the boundary accuracy of the DenseCRF and
+ * DeepLab papers; no reference counterpart: the semantics are fixed here). Integers throughout.
+ * Inputs: labels int32 [n][H][W] (the EVAL branch's prolabels, evaluation cids), decisions int32
+ *   [n][H][W], num_classes nc in 1..256 as for seg_confusion, ignore = a class id or -1 for none,
+ *   widths = w_0 < ... < w_{K-1}, K in 1..8, each w in 1..64. All pointers but widths are device
+ *   memory; widths is read on the host during the call.
+ * Counted label: l with 0 <= l < nc and l != ignore.
+ * Boundary pixel: a pixel that carries a counted label and has at least one 4-neighbour in the
+ *   same image that carries another counted label; both pixels of such a pair are boundary pixels.
+ *   An ignored or out-of-range pixel is never a boundary pixel and never makes a neighbour one.
+ * Squared distance: d2 of a pixel = the minimum of dy^2 + dx^2 over the boundary pixels of the
+ *   same image, capped at 64^2 + 1: no wrap-around, nothing crosses between images of the batch.
+ * Band of width w: the pixels with d2 <= w^2; bands are nested.
+ * Band confusion: cm[k][l][d] = the number of pixels in the band of w_k with labels == l and
+ *   decisions == d, both in [0, nc): the acceptance rule of seg_confusion, ignored labels
+ *   included (the host drops the void row and column of every matrix as it does there).
+ *
+ * seg_boundary_distance: d2_out uint16 [n][H][W] = d2 capped at max_width^2 + 1 instead
+ *   (max_width in 1..64): exact up to max_width^2, and max_width^2 + 1 wherever d2 is larger. The
+ *   one byte per pixel the two passes exchange lives in a buffer of ctx, grown by the call that
+ *   needs more (a device allocation, which synchronises) and freed by seg_destroy.
+ * seg_band_confusion_workspace: the bytes of workspace seg_band_confusion needs (n * H * W rounded
+ *   up to 16). The workspace is the caller's; seg_band_confusion neither allocates nor synchronises.
+ * seg_band_confusion: cm_out int32 [n_widths][nc][nc], overwritten (zeroed on the stream first),
+ *   not accumulated. Two passes sized by w_{K-1}, not by the limit of 64: per row the horizontal
+ *   distance to the nearest boundary pixel, capped at w_{K-1} + 1, one byte per pixel; then per
+ *   pixel the minimum over |dy| <= w_{K-1} of dy^2 + that distance squared, one count in the
+ *   histogram of the smallest band that holds the pixel, and a sum over k at the end. The counts
+ *   are integers, exact in any order.
+ * -EINVAL with a seg_last_error text naming the function and the argument, and no launch, for: a
+ *   null ctx, labels, decisions, widths, workspace, cm_out, d2_out or bytes; n, H or W < 1 (n above
+ *   65535); num_classes outside 1..256; ignore < -1 or >= num_classes; n_widths outside 1..8; a
+ *   width or max_width outside 1..64; widths not strictly increasing; a workspace that is too
+ *   small. */
+int seg_boundary_distance(seg_ctx* ctx, const int32_t* labels, int n, int H, int W,
+                          int num_classes, int ignore, int max_width, uint16_t* d2_out,
+                          void* stream);
+int seg_band_confusion_workspace(int n, int H, int W, int n_widths, int num_classes,
+                                 int64_t* bytes);
+int seg_band_confusion(seg_ctx* ctx, const int32_t* labels, const int32_t* decisions,
+                       int n, int H, int W, int num_classes, int ignore,
+                       const int32_t* widths, int n_widths,
+                       void* workspace, int64_t workspace_bytes,
+                       int32_t* cm_out /* [n_widths][nc][nc] */, void* stream);
+
 /* EVAL / PREDICT (define_estimator_hierarchical.py:161-232) ------------------------------
  * seg_set_bn_inference(ctx, 1): later seg_forward calls normalise with the moving statistics
  * (tf.contrib.layers.batch_norm is_training = batch_norm_accumulate_statistics = False,

@@ -39,6 +39,7 @@ int seg_destroy(seg_ctx* c) {
   (void)hipDeviceSynchronize();
   for (void* p : c->allocs) (void)hipFree(p);
   if (c->infer_jobs) (void)hipFree(c->infer_jobs);
+  if (c->bd_rows) (void)hipFree(c->bd_rows);
   for (auto ev : c->prof.ev) (void)hipEventDestroy(ev);
   for (auto ev : c->bk_ev) (void)hipEventDestroy(ev);
   for (auto ev : c->ev_dy) (void)hipEventDestroy(ev);
@@ -702,6 +703,99 @@ int seg_confusion(seg_ctx* c, const int32_t* labels, const int32_t* decisions, i
   hipError_t e = hipMemsetAsync(cm, 0, (size_t)num_classes * num_classes * 4, s);
   if (e == hipSuccess) e = launch_confusion(labels, decisions, n, num_classes, cm, s);
   if (e != hipSuccess) return hip_fail(c, e, "seg_confusion");
+  return 0;
+}
+
+// What seg_boundary_distance and seg_band_confusion ask of the context, the labels, the size and
+// the classes.
+static int check_boundary_args(seg_ctx* c, const char* who, const int32_t* labels, int n, int H,
+                               int W, int num_classes, int ignore) {
+  if (!c) return set_err(nullptr, -EINVAL, "%s: null ctx", who);
+  std::string* err = &c->err;
+  if (!labels) return set_err(err, -EINVAL, "%s: null labels", who);
+  if (n < 1 || n > BOUNDARY_MAX_IMAGES || H < 1 || W < 1)
+    return set_err(err, -EINVAL, "%s: bad size n = %d, H = %d, W = %d", who, n, H, W);
+  if (num_classes < 1 || num_classes > 256)
+    return set_err(err, -EINVAL, "%s: num_classes = %d (1..256)", who, num_classes);
+  if (ignore < -1 || ignore >= num_classes)
+    return set_err(err, -EINVAL, "%s: ignore = %d (-1 for none, or a class id below num_classes = %d)",
+                   who, ignore, num_classes);
+  return 0;
+}
+
+// the row distances, one byte per pixel, rounded up to 16 bytes
+static int64_t boundary_rows_bytes(int n, int H, int W) {
+  return ((int64_t)n * H * W + 15) / 16 * 16;
+}
+
+int seg_boundary_distance(seg_ctx* c, const int32_t* labels, int n, int H, int W, int num_classes,
+                          int ignore, int max_width, uint16_t* d2_out, void* stream) {
+  const char* who = "seg_boundary_distance";
+  if (int r = check_boundary_args(c, who, labels, n, H, W, num_classes, ignore)) return r;
+  if (max_width < 1 || max_width > BOUNDARY_MAX_WIDTH)
+    return set_err(&c->err, -EINVAL, "%s: max_width = %d (1..%d)", who, max_width, BOUNDARY_MAX_WIDTH);
+  if (!d2_out) return set_err(&c->err, -EINVAL, "%s: null d2_out", who);
+  const size_t need = (size_t)boundary_rows_bytes(n, H, W);
+  if (c->bd_rows_bytes < need) {   // hipFree waits for the launches that still read the old buffer
+    if (c->bd_rows) HIPCALL(c, hipFree(c->bd_rows));
+    c->bd_rows = nullptr; c->bd_rows_bytes = 0;
+    HIPCALL(c, hipMalloc((void**)&c->bd_rows, need));
+    c->bd_rows_bytes = need;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const BoundaryRowArgs ra{labels, n, H, W, num_classes, ignore, max_width, c->bd_rows};
+  HIPCALL(c, launch_boundary_rows(ra, s));
+  BoundaryColArgs ca{};
+  ca.g = c->bd_rows; ca.N = n; ca.H = H; ca.W = W; ca.wmax = max_width; ca.d2 = d2_out;
+  HIPCALL(c, launch_boundary_distance(ca, s));
+  return 0;
+}
+
+int seg_band_confusion_workspace(int n, int H, int W, int n_widths, int num_classes, int64_t* bytes) {
+  if (!bytes || n < 1 || H < 1 || W < 1 || n_widths < 1 || n_widths > BOUNDARY_MAX_WIDTHS ||
+      num_classes < 1 || num_classes > 256)
+    return set_err(nullptr, -EINVAL, "seg_band_confusion_workspace: bad arguments (n %d, H %d, W %d, "
+                   "n_widths %d, num_classes %d%s)", n, H, W, n_widths, num_classes,
+                   bytes ? "" : ", null bytes");
+  *bytes = boundary_rows_bytes(n, H, W);
+  return 0;
+}
+
+int seg_band_confusion(seg_ctx* c, const int32_t* labels, const int32_t* decisions, int n, int H,
+                       int W, int num_classes, int ignore, const int32_t* widths, int n_widths,
+                       void* workspace, int64_t workspace_bytes, int32_t* cm_out, void* stream) {
+  const char* who = "seg_band_confusion";
+  if (int r = check_boundary_args(c, who, labels, n, H, W, num_classes, ignore)) return r;
+  std::string* err = &c->err;
+  if (!decisions) return set_err(err, -EINVAL, "%s: null decisions", who);
+  if (!widths) return set_err(err, -EINVAL, "%s: null widths", who);
+  if (!workspace) return set_err(err, -EINVAL, "%s: null workspace", who);
+  if (!cm_out) return set_err(err, -EINVAL, "%s: null cm_out", who);
+  if (n_widths < 1 || n_widths > BOUNDARY_MAX_WIDTHS)
+    return set_err(err, -EINVAL, "%s: n_widths = %d (1..%d)", who, n_widths, BOUNDARY_MAX_WIDTHS);
+  BoundaryColArgs ca{};
+  for (int k = 0; k < BOUNDARY_MAX_WIDTHS; ++k) ca.w2[k] = INT_MAX;
+  for (int k = 0; k < n_widths; ++k) {
+    if (widths[k] < 1 || widths[k] > BOUNDARY_MAX_WIDTH)
+      return set_err(err, -EINVAL, "%s: widths[%d] = %d (1..%d)", who, k, widths[k], BOUNDARY_MAX_WIDTH);
+    if (k && widths[k] <= widths[k - 1])
+      return set_err(err, -EINVAL, "%s: widths must be strictly increasing (widths[%d] = %d after %d)",
+                     who, k, widths[k], widths[k - 1]);
+    ca.w2[k] = widths[k] * widths[k];
+  }
+  const int64_t need = boundary_rows_bytes(n, H, W);
+  if (workspace_bytes < need)
+    return set_err(err, -EINVAL, "%s: workspace of %lld bytes, %lld needed (seg_band_confusion_workspace)",
+                   who, (long long)workspace_bytes, (long long)need);
+  hipStream_t s = (hipStream_t)stream;
+  const int wmax = widths[n_widths - 1];
+  const BoundaryRowArgs ra{labels, n, H, W, num_classes, ignore, wmax, static_cast<uint8_t*>(workspace)};
+  ca.g = ra.g; ca.N = n; ca.H = H; ca.W = W; ca.wmax = wmax;
+  ca.labels = labels; ca.decisions = decisions; ca.nc = num_classes; ca.K = n_widths; ca.cm = cm_out;
+  HIPCALL(c, hipMemsetAsync(cm_out, 0, (size_t)n_widths * num_classes * num_classes * sizeof(int32_t), s));
+  HIPCALL(c, launch_boundary_rows(ra, s));
+  HIPCALL(c, launch_band_confusion(ca, s));
+  HIPCALL(c, launch_band_finalize(cm_out, n_widths, num_classes, s));
   return 0;
 }
 

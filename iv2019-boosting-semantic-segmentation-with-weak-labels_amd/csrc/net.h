@@ -16,6 +16,7 @@
 #include "../../include/seg_hip.h"
 #include "bn.h"
 #include "bootstrap.h"
+#include "boundary.h"
 #include "boxlabel.h"
 #include "lbf.h"
 #include "input.h"
@@ -182,6 +183,9 @@ struct seg_ctx {
   unsigned* bs_slab = nullptr;
   BootstrapState* bs_state = nullptr;
   int64_t bootstrap_launches = 0;  // seg_loss calls that ran map + select + gated head (seg_counter)
+  // seg_boundary_distance: the row distances g [n][H][W] bytes of the last call, grown on demand
+  uint8_t* bd_rows = nullptr;
+  size_t bd_rows_bytes = 0;
   // update
   int nesterov = 0;               // MomentumOptimizer use_nesterov (seg_set_nesterov)
   int* skip_flag = nullptr;       // device: non-finite scaled gradients this step (update skipped)

@@ -149,8 +149,12 @@ def _eval_spec(predictions, labels, config, params, proimages=None):
     proimages then is (estimator/windows.py, seg_window_decisions). With params.crf_iterations > 0
     the probabilities of whichever of the three paths is active are refined by the mean-field CRF
     on proimages before the argmax (estimator/crf.py, seg_crf_decisions). estimator/inference.py
-    picks among them."""
+    picks among them. With params.boundary_widths the metric ops also hold
+    'band_confusion_matrices', int32 [K, nc, nc]: the confusion matrix over the pixels within each
+    width of a label boundary (estimator/boundary.py, seg_band_confusion), from the same labels
+    and decisions, on the device."""
     import torch
+    from estimator.boundary import band_confusion, boundary_settings
     from estimator.inference import decide_batch
     from utils.utils import _replacevoids
     if getattr(params, 'preserve_aspect_ratio', False):
@@ -164,11 +168,15 @@ def _eval_spec(predictions, labels, config, params, proimages=None):
     decide_batch(predictions, proimages, ctx, config, params, ModeKeys.EVAL, tcids2ecids, decs, replace)
     nc = max(_replacevoids(tcids2ecids)) + 1
     cm = torch.empty((nc, nc), dtype=torch.int32, device=prolabels.device)
-    ctx.confusion(prolabels.to(torch.int32).contiguous(), decs, nc, cm)
+    labs = prolabels.to(torch.int32).contiguous()
+    ctx.confusion(labs, decs, nc, cm)
+    metric_ops = {'confusion_matrix': cm}
+    widths = boundary_settings(params)
+    if widths is not None:   # --boundary_widths: the same matrix per band around the label boundaries
+        metric_ops['band_confusion_matrices'] = band_confusion(ctx, labs, decs, nc, params, widths)
     out = predictions.materialised() if hasattr(predictions, 'materialised') else dict(predictions)
     out['decisions'] = decs
-    return EstimatorSpec(ModeKeys.EVAL, out, losses['total'], None, losses,
-                         {'confusion_matrix': cm})
+    return EstimatorSpec(ModeKeys.EVAL, out, losses['total'], None, losses, metric_ops)
 
 
 def _predict_spec(predictions, features, params, config=None):

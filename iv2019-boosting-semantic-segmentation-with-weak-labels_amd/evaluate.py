@@ -4,7 +4,9 @@ Same command line: ``python evaluate.py <log_dir> <Neval> <training_problem_def_
 {cityscapes,vistas} [--ckpt_path P | --eval_all_ckpts] [--evaluation_problem_def_path P]
 [--replace_voids] [--Nb N]`` plus the model flags and ``[--tta_scales S [S ...]] [--tta_flip]``
 (multi-scale and flip inference, estimator/tta.py; off by default) and ``[--window_canvas HC WC]
-[--window_stride SY SX]`` (sliding-window inference, estimator/windows.py; off by default). The reference's own ``__main__`` raises
+[--window_stride SY SX]`` (sliding-window inference, estimator/windows.py; off by default) and
+``[--boundary_widths W [W ...]]`` (boundary-band accuracy, estimator/boundary.py; off by default:
+``boundary_metrics.txt`` and two more arrays in ``all_metrics.npz``). The reference's own ``__main__`` raises
 NotImplementedError (evaluate.py:81-83); here ``main`` runs: checkpoints written by train.py
 (``<log_dir>/model.ckpt-<step>.pt``) are evaluated on the eval input_fn (seeded synthetic
 Cityscapes-shaped batches, or ``--tfrecords_path`` TFRecords of KEYS2FEATURES_v5 examples), the confusion matrices are
@@ -42,6 +44,7 @@ def _add_extra_args(args):
 
 
 def build_arguments():
+    from estimator.boundary import add_boundary_arguments
     from estimator.crf import add_crf_arguments
     from estimator.tta import add_tta_arguments
     from estimator.windows import add_window_arguments
@@ -55,6 +58,7 @@ def build_arguments():
     add_tta_arguments(ssargs.argparser)
     add_window_arguments(ssargs.argparser)
     add_crf_arguments(ssargs.argparser)
+    add_boundary_arguments(ssargs.argparser)
     return ssargs
 
 
@@ -66,6 +70,8 @@ def main(argv, max_steps=None):
     window_settings(args)   # refuses --tta_scales with --window_canvas before anything is built
     from estimator.crf import crf_settings
     crf_settings(args)   # refuses a bad --crf_* value the same way
+    from estimator.boundary import band_metrics_lines, boundary_settings
+    widths = boundary_settings(args)   # ... and a bad --boundary_widths
     system = SemanticSegmentation({'eval': tfrecord_eval_fn if args.tfrecords_path else eval_fn},
                                   model_fn, args)
     all_metrics = system.evaluate(max_steps=max_steps)
@@ -80,9 +86,16 @@ def main(argv, max_steps=None):
             print(f"{m['global_step']:>05} ", end='', file=f)
             print_metrics_from_confusion_matrix(m['confusion_matrix'], labels, printfile=f)
     import numpy as np
-    np.savez(os.path.join(res_dir, 'all_metrics.npz'),
-             global_step=np.array([m['global_step'] for m in all_metrics]),
-             confusion_matrix=np.stack([m['confusion_matrix'] for m in all_metrics]))
+    arrays = dict(global_step=np.array([m['global_step'] for m in all_metrics]),
+                  confusion_matrix=np.stack([m['confusion_matrix'] for m in all_metrics]))
+    if widths is not None:   # --boundary_widths: two more arrays and a file of their own
+        arrays['boundary_widths'] = np.array(widths, dtype=np.int32)
+        arrays['band_confusion_matrix'] = np.stack([m['band_confusion_matrices'] for m in all_metrics])
+        with open(os.path.join(res_dir, 'boundary_metrics.txt'), 'w') as f:
+            for m in all_metrics:
+                for line in band_metrics_lines(m['global_step'], widths, m['band_confusion_matrices']):
+                    print(line, file=f)
+    np.savez(os.path.join(res_dir, 'all_metrics.npz'), **arrays)
     return all_metrics
 
 

@@ -39,6 +39,7 @@ EXPORTED_SYMBOLS = [
     "seg_window_images", "seg_window_decisions",
     "seg_crf_workspace", "seg_crf_decisions",
     "seg_box_kinds", "seg_box_constrain", "seg_box_decisions", "seg_box_finalize",
+    "seg_boundary_distance", "seg_band_confusion_workspace", "seg_band_confusion",
 ]
 
 # int (*seg_allreduce_fn)(void* user, float* buf, int64_t n, void* stream)
@@ -214,6 +215,10 @@ def _load():
         "seg_box_constrain": (ip, [vp, vp, ip, ip, ip, vp, vp, vp, vp, ip, vp, vp, vp]),
         "seg_box_decisions": (ip, [vp, vp, ip, ip, ip, vp, vp, vp, vp, ip, f, vp, vp, vp, vp]),
         "seg_box_finalize": (ip, [vp, vp, ip, ip, ip, vp, vp, vp, vp, ip, vp, ip, ip, vp, vp]),
+        "seg_boundary_distance": (ip, [vp, vp, ip, ip, ip, ip, ip, ip, vp, vp]),
+        "seg_band_confusion_workspace": (ip, [ip, ip, ip, ip, ip, ctypes.POINTER(i64)]),
+        "seg_band_confusion": (ip, [vp, vp, vp, ip, ip, ip, ip, ip, ctypes.POINTER(ctypes.c_int32), ip,
+                                    vp, i64, vp, vp]),
     }
     override = "SEG_HIP_LIB" in os.environ   # A/B builds of older commits may lack new entries
     for name, (res, args) in sig.items():
@@ -238,6 +243,14 @@ def crf_workspace_bytes(n: int, H: int, W: int, ct: int) -> int:
     """seg_crf_workspace: bytes of the two Q buffers of ``SegContext.crf_decisions``."""
     b = ctypes.c_int64()
     check(LIB.seg_crf_workspace(int(n), int(H), int(W), int(ct), ctypes.byref(b)))
+    return b.value
+
+
+def band_confusion_workspace_bytes(n: int, H: int, W: int, n_widths: int, num_classes: int) -> int:
+    """seg_band_confusion_workspace: bytes of the workspace of ``SegContext.band_confusion``."""
+    b = ctypes.c_int64()
+    check(LIB.seg_band_confusion_workspace(int(n), int(H), int(W), int(n_widths), int(num_classes),
+                                           ctypes.byref(b)))
     return b.value
 
 
@@ -712,6 +725,46 @@ class SegContext:
     def confusion(self, labels, decisions, num_classes, out, stream=None):
         check(LIB.seg_confusion(self.h, _ptr(labels), _ptr(decisions), labels.numel(),
                                 num_classes, _ptr(out), _stream(stream)), self.h)
+
+    def boundary_distance(self, labels, num_classes, ignore, max_width, out=None, stream=None):
+        """seg_boundary_distance: per pixel of ``labels`` (contiguous device int32 [n, H, W]) the
+        squared distance to the nearest boundary pixel of its image, capped at ``max_width``^2 + 1
+        (``max_width`` 1..64). A boundary pixel carries a counted label (0 <= l < ``num_classes``,
+        l != ``ignore``; ``ignore`` -1 for none) and has a 4-neighbour with another counted label.
+        ``out``: device int16 [n, H, W] holding the uint16 values (at most 4097: never negative),
+        allocated when None. Returns ``out``."""
+        import torch
+        _check_tensor(labels, torch.int32, 3, None, "labels")
+        n, H, W = (int(v) for v in labels.shape)
+        if out is None:
+            out = torch.empty((n, H, W), dtype=torch.int16, device=labels.device)
+        _check_tensor(out, torch.int16, 3, n, "out", (H, W))
+        check(LIB.seg_boundary_distance(self.h, _ptr(labels), n, H, W, int(num_classes), int(ignore),
+                                        int(max_width), _ptr(out), _stream(stream)), self.h)
+        return out
+
+    def band_confusion(self, labels, decisions, num_classes, ignore, widths, out, stream=None):
+        """seg_band_confusion: ``out`` (device int32 [K, num_classes, num_classes], overwritten) =
+        the confusion matrices of ``labels`` against ``decisions`` (contiguous device int32
+        [n, H, W], seg_confusion's acceptance rule) over the pixels within ``widths[k]`` pixels
+        (Euclidean) of a boundary pixel of ``labels`` (``boundary_distance``). ``widths``: 1..8
+        strictly increasing integers in 1..64. The workspace is kept on the context per (n, H, W),
+        the way the CRF driver keeps its own."""
+        import torch
+        _check_tensor(labels, torch.int32, 3, None, "labels")
+        n, H, W = (int(v) for v in labels.shape)
+        _check_tensor(decisions, torch.int32, 3, n, "decisions", (H, W))
+        widths = [int(w) for w in widths]
+        nc = int(num_classes)
+        _check_tensor(out, torch.int32, 3, len(widths), "out", (nc, nc))
+        cache = self.__dict__.setdefault("_band_workspaces", {})
+        if (n, H, W) not in cache:
+            nbytes = band_confusion_workspace_bytes(n, H, W, max(len(widths), 1), nc)
+            cache[(n, H, W)] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        ws = cache[(n, H, W)]
+        check(LIB.seg_band_confusion(self.h, _ptr(labels), _ptr(decisions), n, H, W, nc, int(ignore),
+                                     (ctypes.c_int32 * len(widths))(*widths), len(widths), _ptr(ws),
+                                     ws.numel(), _ptr(out), _stream(stream)), self.h)
 
     def debug_tensor(self, name: str):
         """Host copy (float32, [N,H,W,C]) of an internal tensor (parity tests only)."""

@@ -280,7 +280,10 @@ class SemanticSegmentation(object):
 
     def evaluate(self, max_steps=None, log_fn=print):
         """One pass over the eval input per checkpoint; returns [{'global_step', 'loss',
-        'confusion_matrix'}] with the void row/column dropped as the reference does."""
+        'confusion_matrix'}] with the void row/column dropped as the reference does. With
+        --boundary_widths (estimator/boundary.py) every dict also holds 'boundary_widths' and
+        'band_confusion_matrices' (int32 [K, nc, nc], void dropped alike), and one block per
+        width is printed after the whole-image one."""
         import numpy as np
         import torch
         from models.resnet50_extended_model_hierarchical import get_context
@@ -302,10 +305,12 @@ class SemanticSegmentation(object):
             if not ckpts:
                 raise ValueError(f'--eval_all_ckpts: no checkpoints in log_dir {s.log_dir}')
         ctx = get_context(config, s, mode=ModeKeys.EVAL)
+        from estimator.boundary import boundary_settings
+        widths = boundary_settings(s)
         all_metrics = []
         for cp in ckpts:
             gstep = self._restore_for_eval(ctx, cp)
-            cm = None
+            cm, bands = None, None
             data = iter(self._input_fns['eval'](config, s))
             for _ in range(s.num_eval_steps):
                 features, labels = next(data)
@@ -313,12 +318,26 @@ class SemanticSegmentation(object):
                                           params=s)
                 c = spec.eval_metric_ops['confusion_matrix'].to(torch.int64)
                 cm = c if cm is None else cm + c
+                if widths is not None:
+                    b = spec.eval_metric_ops['band_confusion_matrices'].to(torch.int64)
+                    bands = b if bands is None else bands + b
             cm = cm.cpu().numpy().astype(np.int32)
             if void_exists and not getattr(s, 'train_void_class', False):
                 cm = cm[:-1, :-1]
             metrics = {'global_step': gstep, 'loss': 0.0, 'confusion_matrix': cm}
             print_metrics_from_confusion_matrix(np.asarray(cm), labels_names,
                                                 printcmd=bool(log_fn))
+            if widths is not None:
+                bands = bands.cpu().numpy().astype(np.int32)
+                if void_exists and not getattr(s, 'train_void_class', False):
+                    bands = bands[:, :-1, :-1]
+                metrics['boundary_widths'] = list(widths)
+                metrics['band_confusion_matrices'] = bands
+                for w, bcm in zip(widths, bands):
+                    if log_fn:
+                        print(f"Band w = {w}:")
+                    print_metrics_from_confusion_matrix(np.ascontiguousarray(bcm), labels_names,
+                                                        printcmd=bool(log_fn))
             all_metrics.append(metrics)
         return all_metrics
 
